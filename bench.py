@@ -1,7 +1,21 @@
 #!/usr/bin/env python
 """Benchmarks of the batched DSP hot path on 1/2/4/8 MI355X (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config north_star|cfg4|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config north_star|cfg4|cfg5] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set-up, one untimed set-up call, W warm-up steps, exactly K
+timed steps, the outputs of the last timed step to DIR when ``--dump-outputs`` is given, ONE JSON line (metric, value, unit,
+higher_is_better, dtype, ms_per_step, the per-kernel HIP-event averages of the same K steps).  ``--full`` adds everything that
+takes runs, host time or files of its own: the parity of the benchmarked outputs against the oracle (a failed check fails the
+run), "roofline" with the floor twin, the plain-allocation pass, the device copy rate and the replayed counters, the 8-GPU share,
+the (512, 128) variant of cfg5, and "cpu_baseline"; ``--no-cpu-baseline``, ``--no-probes`` and ``--no-share`` trim a ``--full``
+run and mean nothing without it.
+
+``--dump-outputs DIR`` writes what a caller of the timed path holds after the last timed step as ``DIR/<name>.npy`` (float32;
+complex values as (re, im) pairs; ``<name>.rank<r>.npy`` when there is more than one rank): whole arrays up to DUMP_ELEMS
+elements, of larger ones the DUMP_ELEMS elements at fixed, seeded positions (the same positions for the same shape, so two
+builds can be compared element for element; at most 48 MiB = 50.3 MB per configuration).  The inputs are seeded: the same arguments give
+the same inputs in every run.
 
 ``--gpus N`` with N > 1 and no torchrun environment re-launches this script under
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`` (one
@@ -27,7 +41,7 @@ Python dispatch (~0.15 ms per step) is hidden even at 64 items per GPU (0.44 ms 
 (0.475 vs 0.437 ms per step at 64 items, 2.86 vs 2.82 ms at 512: profiles/r02_notes.md), so it is
 not the default.
 
-JSON extras: "roofline" (algorithmic HBM bytes of the dominant kernel / its HIP-event duration vs
+JSON extras of ``--full``: "roofline" (algorithmic HBM bytes of the dominant kernel / its HIP-event duration vs
 8 TB/s) and "cpu_baseline" (the oracle's port of the reference's CPU path -- bit-equal to the
 unmodified reference for stft/mel, <= 1e-5 LU for loudness, tests/test_oracle_vs_reference.py --
 timed on the host cores on a bounded sample; rank 0, N = 1 only).
@@ -244,6 +258,32 @@ def parity_device_north_star(x, sr, mel, stft, chunk=16):
     return bool(e_s < 1e-4 and e_m < 1e-4), e_s, e_m, n
 
 
+# ----------------------------------------------------------------------------- the outputs of the timed path, on disk
+DUMP_ELEMS = 4 << 20    # elements written per array: three arrays, one of them complex, stay below 64 MB
+
+
+def dump_outputs(dirname, arrays, rank, world):
+    """``--dump-outputs``: every tensor of ``arrays`` (what the last timed step handed its caller) as ``<name>.npy`` in float32.
+    An array of more than DUMP_ELEMS elements is sampled at DUMP_ELEMS positions of its LOGICAL shape drawn once from a fixed
+    seed (sorted; the same positions whenever the shape is the same), gathered on the device."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_ELEMS:
+            flat = torch.randint(t.numel(), (DUMP_ELEMS,), generator=torch.Generator().manual_seed(4321)).sort().values.to(t.device)
+            coords = []
+            for size in reversed(t.shape):
+                coords.append(flat % size)
+                flat = flat // size
+            t = t[tuple(reversed(coords))]
+        if t.is_complex():
+            t = torch.view_as_real(t.resolve_conj())
+        path = os.path.join(dirname, f"{name}.npy" if world == 1 else f"{name}.rank{rank}.npy")
+        np.save(path, t.float().cpu().numpy())
+
+
 # ----------------------------------------------------------------------------- launching
 def respawn_under_torchrun(n):
     """python bench.py --gpus N without a torchrun environment: start N ranks on this node."""
@@ -323,6 +363,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="north_star", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=None, help="GLOBAL batch (items); default: the configuration's")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step as DIR/<name>.npy (float32; arrays of "
+                         "more than DUMP_ELEMS elements as a fixed, seeded sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: parity against the oracle, roofline (floor twin, plain-allocation "
+                         "pass, copy rate, replayed counters), the 8-GPU share, the CPU baseline")
     ap.add_argument("--cpu-items", type=int, default=None)
     ap.add_argument("--cpu-iters", type=int, default=3)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -349,6 +395,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launch path only (process group, sharding, table broadcast; gloo on a CPU-only host): no kernels")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(respawn_under_torchrun(args.gpus))
@@ -397,6 +445,34 @@ def main():
            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
            "setup": "one untimed set-up call before the W warm-up steps (tables, workspaces, with --placement on the calibration of the output pool)"}
     kw_cpu = None
+
+    def report():
+        """The end of every run, plain or --full: rank 0 prints the line, every rank leaves the process group."""
+        if rank == 0:
+            out["ms_per_step"] = 1e3 * elapsed / args.steps
+            out["value"] = batch * dur / (elapsed / args.steps)
+            out["world_size"] = world
+            out["backend"] = torch.distributed.get_backend() if (world > 1 or args.force_nccl) else None
+            out["per_rank_ms_per_step"] = [1e3 * t / args.steps for t in PER_RANK_S]
+            if PER_RANK_S:
+                out["rank_skew"] = {"min_ms_per_step": 1e3 * min(PER_RANK_S) / args.steps, "max_ms_per_step": 1e3 * max(PER_RANK_S) / args.steps,
+                                    "max_over_min": max(PER_RANK_S) / min(PER_RANK_S)}
+            out["host"] = socket.gethostname()
+            out["lib_sha256"] = lib_sha256()
+            if rccl_contact is not None:
+                out["rccl_contact"] = rccl_contact
+            if args.full and world == 1 and not args.no_cpu_baseline:
+                if args.config == "north_star":
+                    out["cpu_baseline"] = cpu_baseline_north_star(args.cpu_items or 64, args.cpu_iters)
+                else:
+                    out["cpu_baseline"] = cpu_baseline_cfg(args.config, kw_cpu, args.cpu_items or (8 if args.config == "cfg4" else 4))
+                out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
+            print(json.dumps(out))
+        if world > 1 or args.force_nccl:
+            adist.barrier()            # the other ranks wait here while rank 0 takes its evidence and prints the line
+            torch.distributed.destroy_process_group()
+        if rank == 0 and not out.get("parity_check", {"ok": True})["ok"]:
+            sys.exit("bench.py: the benchmarked outputs differ from the oracle beyond the tolerance (parity_check above)")
 
     if args.config == "north_star":
         sig = A.AudioSignal(x, sr)
@@ -462,6 +538,19 @@ def main():
         lufs_ms = sum(e[1].elapsed_time(e[2]) for e in events) / len(events)
         mel, lufs = res["mel"], res["lufs"]
         assert torch.isfinite(mel).all() and torch.isfinite(lufs).all()
+        if args.dump_outputs:      # (before anything of --full runs: the floor twin leaves garbage in the spectrum buffer)
+            dump_outputs(args.dump_outputs, {"mel": mel, "stft": sig.stft_data, "lufs": lufs}, rank, world)
+        out["config"] = {"workload": f"north-star: batch={batch} 2ch 10s@44.1kHz mel_spectrogram(80) "
+                                     f"[fused STFT {n_fft}/{hop} hann + mel] + loudness()",
+                         "global_batch": batch, "items_per_gpu": n_local, "parallelism": f"batch-shard x{world}",
+                         "inputs": "device-resident (H2D excluded)", "launch": launch}
+        per_step = sorted(e[0].elapsed_time(e[1]) for e in events)
+        out["kernels_ms"] = {"stft_mel": stft_ms, "stft_mel_min": per_step[0], "stft_mel_median": per_step[len(per_step) // 2],
+                             "stft_mel_max": per_step[-1],
+                             "lufs_total": lufs_ms, "lufs_GBps": lufs_bytes / (lufs_ms * 1e-3) / 1e9,
+                             "timing": timing_note}
+        if not args.full:
+            return report()
         # the 8-GPU share timed on THIS device: what one rank of an 8-way batch shard would run, so that the
         # first measured scaling curve has a prediction to be checked against (no collective on the data path)
         share = None
@@ -622,10 +711,6 @@ def main():
         torch.cuda.synchronize()
         copy_gbs = 5 * 2 * cp_src.numel() * 4 / (ce[0].elapsed_time(ce[1]) * 1e-3) / 1e9
         del cp_dst
-        out["config"] = {"workload": f"north-star: batch={batch} 2ch 10s@44.1kHz mel_spectrogram(80) "
-                                     f"[fused STFT {n_fft}/{hop} hann + mel] + loudness()",
-                         "global_batch": batch, "items_per_gpu": n_local, "parallelism": f"batch-shard x{world}",
-                         "inputs": "device-resident (H2D excluded)", "launch": launch}
         out["roofline"] = {"bound": "hbm", "kernel": "stft_mel_kernel_v2<4> (fused STFT 2048/512 + 80-band mel)",
                            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                            "traffic": traffic, "traffic_source": traffic_src,
@@ -645,11 +730,6 @@ def main():
                                          "deterministic per allocation, profiles/r05_notes.md section 1), so this is the figure that says "
                                          "which regime the kernel of record ran in"}
         out["parity_check"] = parity
-        per_step = sorted(e[0].elapsed_time(e[1]) for e in events)
-        out["kernels_ms"] = {"stft_mel": stft_ms, "stft_mel_min": per_step[0], "stft_mel_median": per_step[len(per_step) // 2],
-                             "stft_mel_max": per_step[-1],
-                             "lufs_total": lufs_ms, "lufs_GBps": lufs_bytes / (lufs_ms * 1e-3) / 1e9,
-                             "timing": timing_note}
         if share is not None:
             out["share_64" if n_local == 512 else f"share_{n_local // 8}"] = share
 
@@ -684,12 +764,21 @@ def main():
             res["y"] = chain(A.AudioSignal(x, sr), **kw).audio_data
 
         elapsed, _ = time_steps(step, args.steps, args.warmup, adist, device, world)
+        assert torch.isfinite(res["y"]).all()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"y": res["y"]}, rank, world)
+        out["config"] = {"workload": f"cfg4: batch={batch} mono 5s@48kHz Compose(LowPass, Equalizer(6), "
+                                     f"RoomImpulseResponse(2 s RIR, DRR, EQ))", "global_batch": batch,
+                         "items_per_gpu": n_local, "parallelism": f"batch-shard x{world} + RCCL broadcast of the IR bank / tables",
+                         "inputs": "device-resident; transform parameters drawn before the timed region",
+                         "host_instantiate_ms": inst_ms}
+        if not args.full:
+            return report()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         step(None)
-        enq_ms = (time.perf_counter() - t0) * 1e3          # host time to enqueue one chain (no sync inside)
+        out["config"]["host_enqueue_ms"] = (time.perf_counter() - t0) * 1e3          # host time to enqueue one chain (no sync inside)
         torch.cuda.synchronize()
-        assert torch.isfinite(res["y"]).all()
         chain_bytes = 3 * 2 * rows * T * 4 + rows * 2 * sr * 4
         achieved = chain_bytes / (elapsed / args.steps) / 1e9
         # parity of the benchmarked launch: the oracle's chain on three of its items (those whose impulse responses
@@ -706,11 +795,6 @@ def main():
             out["parity_check"] = {"items": idx, "chain_rel": c4, "tol": {"chain_rel": 1e-4}, "ok": bool(c4 < 1e-4),
                                    "oracle": "oracle/restate.py low_pass -> equalizer -> apply_ir on the host"}
         traffic, traffic_src, per_kernel = committed_traffic(args.config, n_local, "rowconv_kernel")
-        out["config"] = {"workload": f"cfg4: batch={batch} mono 5s@48kHz Compose(LowPass, Equalizer(6), "
-                                     f"RoomImpulseResponse(2 s RIR, DRR, EQ))", "global_batch": batch,
-                         "items_per_gpu": n_local, "parallelism": f"batch-shard x{world} + RCCL broadcast of the IR bank / tables",
-                         "inputs": "device-resident; transform parameters drawn before the timed region",
-                         "host_instantiate_ms": inst_ms, "host_enqueue_ms": enq_ms}
         out["roofline"] = {"bound": "hbm", "kernel": "whole chain (fir_fft x3, alter_drr, absmax, roll_pad, four-step FFT convolution: colfft x3 + rowconv)",
                            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                            "traffic": None, "algorithmic_bytes_per_launch": chain_bytes,
@@ -735,11 +819,20 @@ def main():
             if ev is not None:
                 ev[2].record()
 
-        _, events = time_steps(step, max(3, min(args.steps, 10)), args.warmup, adist, device, world, n_events=3)
-        rs_ms = sum(e[0].elapsed_time(e[1]) for e in events) / len(events)
-        mel_ms = sum(e[1].elapsed_time(e[2]) for e in events) / len(events)
+        if args.full:      # the per-kernel durations of the roofline block: a pass of its own, before the timed one
+            _, events = time_steps(step, max(3, min(args.steps, 10)), args.warmup, adist, device, world, n_events=3)
+            rs_ms = sum(e[0].elapsed_time(e[1]) for e in events) / len(events)
+            mel_ms = sum(e[1].elapsed_time(e[2]) for e in events) / len(events)
         elapsed, _ = time_steps(step, args.steps, args.warmup, adist, device, world)
         assert torch.isfinite(res["mel"]).all()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"y": res["y"], "mel": res["mel"]}, rank, world)
+        out["config"] = {"workload": f"cfg5: batch={batch} 2ch 30s@44.1kHz resample(16000) + mel_spectrogram(80) "
+                                     f"[STFT 2048/512 as the signal keeps its stft_params]", "global_batch": batch,
+                         "items_per_gpu": n_local, "parallelism": f"batch-shard x{world} + RCCL broadcast of the resample bank / tables",
+                         "inputs": "device-resident (H2D excluded)"}
+        if not args.full:
+            return report()
         T2 = int(16000 * T // sr)
         n_frames = 1 + T2 // 512
         rs_bytes = rows * T * 4 + rows * T2 * 4
@@ -753,10 +846,6 @@ def main():
             e_rs, e_mel = rel_rows(res["y"][idx].cpu(), yo), rel_rows(res["mel"][idx].cpu(), mo)
             out["parity_check"] = {"items": idx, "resample_rel": e_rs, "mel_rel": e_mel, "tol": {"resample_rel": 1e-4, "mel_rel": 1e-4},
                                    "ok": bool(e_rs < 1e-4 and e_mel < 1e-4), "oracle": "oracle/restate.py resample -> stft -> mel on the host"}
-        out["config"] = {"workload": f"cfg5: batch={batch} 2ch 30s@44.1kHz resample(16000) + mel_spectrogram(80) "
-                                     f"[STFT 2048/512 as the signal keeps its stft_params]", "global_batch": batch,
-                         "items_per_gpu": n_local, "parallelism": f"batch-shard x{world} + RCCL broadcast of the resample bank / tables",
-                         "inputs": "device-resident (H2D excluded)"}
         from audiotools_amd import kernels as K5
         form = K5.resample_first_form(441, 160)            # the dispatcher's own predicate
         if form == "f16":
@@ -792,31 +881,7 @@ def main():
             out["kernels_ms"]["stft_mel_512_128_GBps"] = b5 / (ms5 * 1e-3) / 1e9
             del s16
 
-    if rank == 0:
-        out["ms_per_step"] = 1e3 * elapsed / args.steps
-        out["value"] = batch * dur / (elapsed / args.steps)
-        out["world_size"] = world
-        out["backend"] = torch.distributed.get_backend() if (world > 1 or args.force_nccl) else None
-        out["per_rank_ms_per_step"] = [1e3 * t / args.steps for t in PER_RANK_S]
-        if PER_RANK_S:
-            out["rank_skew"] = {"min_ms_per_step": 1e3 * min(PER_RANK_S) / args.steps, "max_ms_per_step": 1e3 * max(PER_RANK_S) / args.steps,
-                                "max_over_min": max(PER_RANK_S) / min(PER_RANK_S)}
-        out["host"] = socket.gethostname()
-        out["lib_sha256"] = lib_sha256()
-        if rccl_contact is not None:
-            out["rccl_contact"] = rccl_contact
-        if world == 1 and not args.no_cpu_baseline:
-            if args.config == "north_star":
-                out["cpu_baseline"] = cpu_baseline_north_star(args.cpu_items or 64, args.cpu_iters)
-            else:
-                out["cpu_baseline"] = cpu_baseline_cfg(args.config, kw_cpu, args.cpu_items or (8 if args.config == "cfg4" else 4))
-            out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
-        print(json.dumps(out))
-    if world > 1 or args.force_nccl:
-        adist.barrier()            # the other ranks wait here while rank 0 takes its evidence and prints the line
-        torch.distributed.destroy_process_group()
-    if rank == 0 and not out.get("parity_check", {"ok": True})["ok"]:
-        sys.exit("bench.py: the benchmarked outputs differ from the oracle beyond the tolerance (parity_check above)")
+    report()
 
 
 if __name__ == "__main__":
