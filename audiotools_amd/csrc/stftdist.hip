@@ -1,0 +1,378 @@
+// Fused multi-scale STFT distance for gfx950: loss sums and dL/dX of ONE scale in one kernel.
+//
+// Replaces, per scale of  reference audiotools/metrics/spectral.py:11-94  (MultiScaleSTFTLoss with an L1 loss_fn):
+//   two stft() calls, abs / clamp / pow / log10 / sub / abs / mean on both spectra, and the autograd replay of all of them.
+// The distance is a function of two SIGNALS: the kernel reads x and y once, never writes a spectrum of either, and the only
+// large object it produces is G = dL/dX (when a gradient is wanted), in the layout at_stft_adjoint_f32 reads.
+//
+// Design (CDNA4), on the wave FFT of fft_wave.h -- the work split of the forward kernels in stft.hip:
+//  * M = n_fft/2 complex points, every thread owns 16 of them, L = M/16 lanes form a frame, a wave64 holds 64/L frames;
+//    Stockham passes of radix 16 / R2 / R3 through the wave's LDS slab, then the real-FFT split step;
+//  * persistent grid; every wave owns ONE contiguous run of frame groups (rows in order, frames in order), so the 3/4
+//    overlap between consecutive frames is served by the caches and HBM sees each sample about once;
+//  * BOTH signals in one wave: the samples of the y and x frames of a group are loaded together (the x loads are in flight
+//    during y's transform); y is transformed first and only |Y| and c log2 max(|Y|^2, eps^2) of the lane's 17 bins stay in
+//    registers; x goes through the same slab.  After the split bin k of X sits in the lane and slot of bin k of Y, so
+//    the comparison, both sums and G are lane-local: no magnitude ever goes through LDS or memory;
+//  * log term from |.|^2 with v_log_f32, |.| with v_sqrt_f32, 1/|X| with v_rsq_f32 (1 ulp each; no IEEE expansions);
+//  * G leaves through the slab as 512-byte non-temporal runs (bin-contiguous (rows, N, F)); without G there is no large store;
+//  * two float accumulators per lane over the whole run, one wave reduction, one partial pair per wave in the workspace;
+//    a one-workgroup kernel adds the partials in double in a fixed order: no atomics, bit-equal sums on every run;
+//  * frame slots past a row's last frame repeat that frame (as in stft.hip) but add nothing and store nothing.
+#include "at_common.h"
+#include "fft_wave.h"
+#include <float.h>
+
+extern "C" int at_stft_fused_supported(int n_fft);
+
+namespace {
+
+constexpr int NW = 4;              // waves per workgroup
+constexpr int MAX_BLOCKS = 1024;   // persistent grid bound the workspace is sized for (2 per CU on 512 CUs)
+
+struct DistArgs {
+  const float* x;          // (rows, T) estimate
+  const float* y;          // (rows, T) target
+  const float* window;     // (n_fft)
+  const float2* tw;        // (n_fft): (cos, -sin)(2 pi k / n_fft)
+  float2* G;               // (rows, n_out, M+1) or null
+  float2* partials;        // (gridDim.x * NW) {sum log, sum mag}
+  int T;
+  int n_out;               // frames per row
+  int hop;
+  int gpr;                 // frame groups per row: ceil(n_out / FW)
+  int64_t total_groups;    // rows * gpr
+  float eps, eps2;         // clamp_eps and its square
+  float c_log;             // 0.5 * power * log10(2):  c_log * log2(|X|^2) = power * log10 |X|
+  float g_logp;            // g_log * power / ln 10
+  float g_mag;
+  int vec2;                // rows of x and y are 8-byte aligned: float2 loads
+};
+
+template <int M>
+constexpr int lds_floats() { return NW * 2 * WAVE_LDS_SLOTS + 2 * M + M + 16 * 36; }
+
+__device__ __forceinline__ float abs2(float2 z) { return fmaf(z.x, z.x, z.y * z.y); }
+__device__ __forceinline__ float sgnf(float a, float b) { return (a > b ? 1.f : 0.f) - (a < b ? 1.f : 0.f); }
+
+template <int M, bool GRAD>
+__global__ __launch_bounds__(NW * 64, 2) void stft_dist_kernel(const DistArgs A) {
+  using P = Plan<M>;
+  constexpr int L = P::L, FW = P::FW, N = 2 * M;
+  // LDS (floats): [NW wave slabs][window, halved: 2M][split twiddles: M][pass-2 twiddles: 16 rows x 36]
+  extern __shared__ __attribute__((aligned(16))) float lds_f[];
+  float* s_win = lds_f + NW * 2 * WAVE_LDS_SLOTS;
+  float2* s_twp = reinterpret_cast<float2*>(s_win + N);
+  float* s_tw2 = s_win + N + M;
+  // the factor 1/2 of the split step rides on the window (exact in binary floating point)
+  for (int i = threadIdx.x; i < N; i += NW * 64) s_win[i] = 0.5f * A.window[i];
+  for (int i = threadIdx.x; i < M / 2; i += NW * 64) s_twp[i] = A.tw[i];
+  if constexpr (P::R2 > 1) {
+    for (int i = threadIdx.x; i < 16 * P::R2; i += NW * 64) {
+      const int jj = i / P::R2, r = i % P::R2;
+      reinterpret_cast<float2*>(s_tw2 + jj * 36)[r] = A.tw[r * jj * (N / (16 * P::R2))];
+    }
+  }
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int fs = lane / L;  // frame slot inside the wave
+  const int t = lane % L;   // thread inside the frame
+  float2* wbuf = reinterpret_cast<float2*>(lds_f) + wave * WAVE_LDS_SLOTS;
+  float2* fbuf = wbuf + fs * P::SLOTS;
+
+  constexpr int NB2 = 16 / P::R2;
+  constexpr int NB3 = 16 / P::R3;
+  float2 tw3b[P::R3 > 1 ? NB3 : 1];  // base twiddle per butterfly of pass 3; its powers are derived
+  if constexpr (P::R3 > 1) {
+    constexpr int NS = 16 * P::R2;
+#pragma unroll
+    for (int b = 0; b < NB3; ++b) tw3b[b] = A.tw[((t + b * L) % NS) * (N / (NS * P::R3))];
+  }
+
+  // ---- samples of this thread's frame: points t + L q of z[n] = s[2n] + i s[2n+1].  Interior frames load directly;
+  // a group that touches a reflected margin takes a rolled loop through the wave's slab (index arithmetic, no copy).
+  auto load_frame = [&](float2 (&a)[16], const float* __restrict__ sr, int s0, bool interior) __attribute__((always_inline)) {
+    if (interior) {
+      if (A.vec2) {
+        const float2* __restrict__ p = reinterpret_cast<const float2*>(sr + s0);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) a[q] = p[t + L * q];
+      } else {
+        const float* __restrict__ p = sr + s0;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) a[q] = make_float2(p[2 * (t + L * q)], p[2 * (t + L * q) + 1]);
+      }
+    } else {
+#pragma unroll 1
+      for (int q = 0; q < 16; ++q) {
+        const int n = t + L * q;
+        int u0 = s0 + 2 * n, u1 = u0 + 1;          // centre reflect padding: one reflection (T > n_fft/2)
+        u0 = u0 < 0 ? -u0 : u0; u0 = u0 >= A.T ? 2 * (A.T - 1) - u0 : u0;
+        u1 = u1 < 0 ? -u1 : u1; u1 = u1 >= A.T ? 2 * (A.T - 1) - u1 : u1;
+        u0 = min(max(u0, 0), A.T - 1); u1 = min(max(u1, 0), A.T - 1);
+        fbuf[n] = make_float2(sr[u0], sr[u1]);
+      }
+      wave_sync();
+#pragma unroll
+      for (int q = 0; q < 16; ++q) a[q] = fbuf[t + L * q];
+      wave_sync();
+    }
+  };
+
+  // ---- window, M-point complex FFT, real-FFT split.  Out: bins k = t + L q in xa[q], bins M - k in xb[q] (thread 0,
+  // q = 0: DC and Nyquist), bin M/2 in xh (thread 0 only; 0 elsewhere).  The slab is free again on return.
+  auto transform = [&](float2 (&a)[16], float2 (&xa)[8], float2 (&xb)[8], float2& xh) __attribute__((always_inline)) {
+    {
+      const float2* w2 = reinterpret_cast<const float2*>(s_win);
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const float2 w = w2[t + L * q];
+        a[q] = make_float2(a[q].x * w.x, a[q].y * w.y);
+      }
+    }
+    pass_compute_store<16, 1, L>(a, fbuf, t, nullptr);
+    wave_sync();
+    if constexpr (P::R2 > 1) {
+      load_points<L>(a, fbuf, t);
+      wave_sync();
+      float2 tw2[NB2 * P::R2];
+#pragma unroll
+      for (int b = 0; b < NB2; ++b) {
+        const float2* rowp = reinterpret_cast<const float2*>(s_tw2 + ((t + b * L) & 15) * 36);
+#pragma unroll
+        for (int r = 1; r < P::R2; ++r) tw2[b * P::R2 + r] = rowp[r];
+      }
+      pass_compute_store<P::R2, 16, L>(a, fbuf, t, tw2);
+      wave_sync();
+    }
+    if constexpr (P::R3 > 1) {
+      load_points<L>(a, fbuf, t);
+      wave_sync();
+      float2 tw3[NB3 * P::R3];
+#pragma unroll
+      for (int b = 0; b < NB3; ++b) {
+        tw3[b * P::R3 + 1] = tw3b[b];
+#pragma unroll
+        for (int r = 2; r < P::R3; ++r) tw3[b * P::R3 + r] = cmul(tw3[b * P::R3 + r - 1], tw3b[b]);
+      }
+      pass_compute_store<P::R3, 16 * P::R2, L>(a, fbuf, t, tw3);
+      wave_sync();
+    }
+    float2 zh = make_float2(0.f, 0.f);
+    if (t == 0) zh = fbuf[phys<L>(M / 2)];
+    xh = make_float2(2.f * zh.x, -2.f * zh.y);       // k == M/2: X = conj(Z[M/2])  (Z carries the halved window)
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int k = t + L * q;
+      const float2 zk = fbuf[phys<L>(k)];
+      const float2 zm = fbuf[phys<L>((M - k) & (M - 1))];
+      if (q == 0 && t == 0) {   // packed point 0: DC and Nyquist, two real bins
+        xa[q] = make_float2(2.f * (zk.x + zk.y), 0.f);
+        xb[q] = make_float2(2.f * (zk.x - zk.y), 0.f);
+      } else {
+        const float2 twp = s_twp[k];  // (cos, -sin)(2 pi k / N)
+        const float sr = zk.x + zm.x, si = zk.y - zm.y;
+        const float dr = zk.x - zm.x, di = zk.y + zm.y;
+        const float c = twp.x, s = -twp.y;
+        const float pp = fmaf(s, dr, -c * di);
+        const float qq = fmaf(s, di, c * dr);
+        xa[q] = make_float2(sr - pp, si - qq);
+        xb[q] = make_float2(sr + pp, -si - qq);
+      }
+    }
+    wave_sync();
+  };
+
+  // ---- this wave's run of frame groups
+  const int64_t n_waves = (int64_t)gridDim.x * NW;
+  const int64_t gw = (int64_t)blockIdx.x * NW + wave;
+  const int64_t g_lo = A.total_groups * gw / n_waves;
+  const int64_t g_hi = A.total_groups * (gw + 1) / n_waves;
+  float s_log = 0.f, s_mag = 0.f;
+
+  for (int64_t g = g_lo; g < g_hi; ++g) {
+    const int64_t row = g / A.gpr;
+    const int gb = (int)(g - row * A.gpr);
+    const int f0 = gb * FW;
+    const bool valid = f0 + fs < A.n_out;
+    const int fo = min(f0 + fs, A.n_out - 1);     // slots past the row's last frame repeat it (and are masked below)
+    const int s0 = fo * A.hop - M;                // first sample of the frame in un-padded coordinates
+    const bool interior = __all(s0 >= 0 && s0 + N <= A.T);
+    float2 ay[16], ax[16];
+    load_frame(ay, A.y + row * A.T, s0, interior);
+    load_frame(ax, A.x + row * A.T, s0, interior);
+
+    // target: keep |Y| and the log term of the lane's 17 bins
+    float yb[17], yl[17];
+    {
+      float2 xa[8], xb[8], xh;
+      transform(ay, xa, xb, xh);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const float pa = abs2(xa[q]), pb = abs2(xb[q]);
+        yb[q] = __builtin_amdgcn_sqrtf(pa);
+        yl[q] = A.c_log * __builtin_amdgcn_logf(fmaxf(pa, A.eps2));
+        yb[8 + q] = __builtin_amdgcn_sqrtf(pb);
+        yl[8 + q] = A.c_log * __builtin_amdgcn_logf(fmaxf(pb, A.eps2));
+      }
+      const float ph = abs2(xh);
+      yb[16] = __builtin_amdgcn_sqrtf(ph);
+      yl[16] = A.c_log * __builtin_amdgcn_logf(fmaxf(ph, A.eps2));
+    }
+
+    // estimate: compare bin by bin; X is still in registers when G is formed
+    auto bin = [&](float2 X, float b, float lb, bool on) __attribute__((always_inline)) -> float2 {
+      const float a2 = abs2(X);
+      const float a = __builtin_amdgcn_sqrtf(a2);
+      const float la = A.c_log * __builtin_amdgcn_logf(fmaxf(a2, A.eps2));
+      s_log += on ? fabsf(la - lb) : 0.f;
+      s_mag += on ? fabsf(a - b) : 0.f;
+      if constexpr (!GRAD) return X;
+      // 1/|X|; G = 0 where |X|^2 is zero (or below the normal range, where v_rsq_f32 is not defined)
+      const float inv = a2 >= FLT_MIN ? __builtin_amdgcn_rsqf(a2) : 0.f;
+      const float sl = sgnf(fmaxf(a, A.eps), fmaxf(b, A.eps));
+      const float gl = a >= A.eps ? A.g_logp * sl * inv : 0.f;
+      const float coef = fmaf(A.g_mag, sgnf(a, b), gl) * inv;
+      return make_float2(coef * X.x, coef * X.y);
+    };
+    {
+      float2 xa[8], xb[8], xh;
+      transform(ax, xa, xb, xh);
+      float2* sx = wbuf + fs * P::SLOTS;           // G of frame slot fs, bins in order
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int k = t + L * q;
+        const float2 ga = bin(xa[q], yb[q], yl[q], valid);
+        const float2 gb2 = bin(xb[q], yb[8 + q], yl[8 + q], valid);
+        if constexpr (GRAD) { sx[k] = ga; sx[M - k] = gb2; }
+      }
+      const float2 gh = bin(xh, yb[16], yl[16], valid && t == 0);
+      if constexpr (GRAD) {
+        if (t == 0) sx[M / 2] = gh;
+        wave_sync();
+        // the FW frames of the group are consecutive rows of G: (M + 1) FW contiguous float2, streamed as 512-byte runs
+        constexpr int TOT = FW * (M + 1);
+        constexpr int NST = (TOT + 63) / 64;
+        const int tot = min(FW, A.n_out - f0) * (M + 1);       // only the frames that exist
+        float2* __restrict__ obase = A.G + (row * A.n_out + f0) * (M + 1);
+#pragma unroll
+        for (int i = 0; i < NST; ++i) {
+          const int idx = i * 64 + lane;
+          if (idx < tot) {
+            const int f = idx / (M + 1);
+            at::stg2<true>(obase + idx, wbuf[f * P::SLOTS + (idx - f * (M + 1))]);
+          }
+        }
+        wave_sync();
+      }
+    }
+  }
+  s_log = at::wave_sum(s_log);
+  s_mag = at::wave_sum(s_mag);
+  if (lane == 0) A.partials[gw] = make_float2(s_log, s_mag);
+}
+
+// One workgroup: the partial pairs of all waves, added in double in a fixed order (thread i takes i, i + 256, ...; then a
+// fixed tree), so that the same inputs give the same bits on every run.
+__global__ __launch_bounds__(256) void stft_dist_finalize(const float2* __restrict__ partials, int n, double* __restrict__ sums) {
+  __shared__ double sh[2][256];
+  double s0 = 0.0, s1 = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const float2 p = partials[i];
+    s0 += (double)p.x;
+    s1 += (double)p.y;
+  }
+  sh[0][threadIdx.x] = s0;
+  sh[1][threadIdx.x] = s1;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      sh[0][threadIdx.x] += sh[0][threadIdx.x + o];
+      sh[1][threadIdx.x] += sh[1][threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    sums[0] = sh[0][0];
+    sums[1] = sh[1][0];
+  }
+}
+
+template <int M>
+int launch_dist(const DistArgs& A, int blocks, hipStream_t stream) {
+  const size_t bytes = (size_t)lds_floats<M>() * 4;   // <= 49408 B: no raised LDS limit needed
+  if (A.G) hipLaunchKernelGGL((stft_dist_kernel<M, true>), dim3((unsigned)blocks), dim3(NW * 64), bytes, stream, A);
+  else hipLaunchKernelGGL((stft_dist_kernel<M, false>), dim3((unsigned)blocks), dim3(NW * 64), bytes, stream, A);
+  AT_LAUNCH_CHECK();
+  return AT_OK;
+}
+
+// AT_OK when the kernel takes the shape
+int dist_shape_check(int64_t rows, int64_t T, int n_fft, int hop) {
+  if (rows <= 0 || T <= 0 || n_fft <= 0 || hop <= 0) return AT_ERR_INVALID;
+  if (!at_stft_fused_supported(n_fft) || hop * 4 != n_fft || T <= n_fft / 2) return AT_ERR_UNSUPPORTED;
+  const int64_t n_out = 1 + T / hop;
+  if (T >= (1LL << 30) || n_out * (n_fft / 2 + 1) >= (1LL << 31)) return AT_ERR_UNSUPPORTED;   // 32-bit sample / bin indices
+  return AT_OK;
+}
+
+int64_t dist_max_blocks(int64_t rows, int64_t T, int n_fft, int hop) {
+  const int FW = 64 / (n_fft / 32);
+  const int64_t gpr = (1 + T / hop + FW - 1) / FW;
+  const int64_t blocks = (rows * gpr + NW - 1) / NW;
+  return blocks < MAX_BLOCKS ? blocks : MAX_BLOCKS;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t at_stft_dist_workspace_bytes(int64_t rows, int64_t T, int n_fft, int hop) {
+  const int e = dist_shape_check(rows, T, n_fft, hop);
+  if (e != AT_OK) return e;
+  return dist_max_blocks(rows, T, n_fft, hop) * NW * (int64_t)sizeof(float2);
+}
+
+int at_stft_dist_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                     int n_fft, int hop, float clamp_eps, float power, float g_log, float g_mag, float* G, double* sums,
+                     void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!x || !y || !window || !twiddles || !sums || !workspace) return AT_ERR_INVALID;
+  const int e = dist_shape_check(rows, T, n_fft, hop);
+  if (e != AT_OK) return e;
+  if (!(clamp_eps * clamp_eps >= FLT_MIN) || !(power > 0.f)) return AT_ERR_UNSUPPORTED;
+  if (workspace_bytes < at_stft_dist_workspace_bytes(rows, T, n_fft, hop)) return AT_ERR_INVALID;
+  const int M = n_fft / 2, FW = 64 / (M / 16);
+  DistArgs A;
+  A.x = x; A.y = y; A.window = window; A.tw = reinterpret_cast<const float2*>(twiddles);
+  A.G = reinterpret_cast<float2*>(G); A.partials = reinterpret_cast<float2*>(workspace);
+  A.T = (int)T; A.n_out = (int)(1 + T / hop); A.hop = hop;
+  A.gpr = (A.n_out + FW - 1) / FW;
+  A.total_groups = rows * A.gpr;
+  A.eps = clamp_eps; A.eps2 = clamp_eps * clamp_eps;
+  A.c_log = (float)(0.5 * (double)power * 0.30102999566398119521);
+  A.g_logp = (float)((double)g_log * (double)power / 2.30258509299404568402);
+  A.g_mag = g_mag;
+  A.vec2 = ((T % 2) == 0 && (reinterpret_cast<uintptr_t>(x) % 8) == 0 && (reinterpret_cast<uintptr_t>(y) % 8) == 0) ? 1 : 0;
+  int64_t blocks = dist_max_blocks(rows, T, n_fft, hop);
+  const int64_t resident = 2 * (int64_t)at::device_cu_count();      // two workgroups per CU (launch bounds; 49 KB of LDS each)
+  if (blocks > resident) blocks = resident;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  int r = AT_ERR_UNSUPPORTED;
+  switch (M) {
+    case 16: r = launch_dist<16>(A, (int)blocks, s); break;
+    case 32: r = launch_dist<32>(A, (int)blocks, s); break;
+    case 64: r = launch_dist<64>(A, (int)blocks, s); break;
+    case 128: r = launch_dist<128>(A, (int)blocks, s); break;
+    case 256: r = launch_dist<256>(A, (int)blocks, s); break;
+    case 512: r = launch_dist<512>(A, (int)blocks, s); break;
+    case 1024: r = launch_dist<1024>(A, (int)blocks, s); break;
+  }
+  if (r != AT_OK) return r;
+  hipLaunchKernelGGL(stft_dist_finalize, dim3(1), dim3(256), 0, s, A.partials, (int)blocks * NW, sums);
+  AT_LAUNCH_CHECK();
+  return AT_OK;
+}
+
+}  // extern "C"

@@ -610,6 +610,44 @@ def stft_mel_adjoint(X_bcfn: torch.Tensor, gmel_bcmn: torch.Tensor, bin_table, w
     return _fold_reflect(out, T, half)
 
 
+def stft_distance_supported(n_fft: int, hop: int, T: int, clamp_eps: float, power: float) -> bool:
+    """The fused distance kernel (csrc/stftdist.hip) takes this scale: power-of-two n_fft in 32 ... 2048, hop = n_fft / 4,
+    more than n_fft / 2 samples, a clamp whose square is a normal float32, a positive exponent."""
+    return (stft_fused_supported(n_fft) and hop * 4 == n_fft and T > n_fft // 2 and T < 2 ** 30
+            and (1 + T // hop) * (n_fft // 2 + 1) < 2 ** 31
+            and float(clamp_eps) ** 2 >= float(torch.finfo(torch.float32).tiny) and power > 0)
+
+
+def stft_distance(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_fft: int, hop: int, clamp_eps: float,
+                  power: float, g_log: float, g_mag: float, want_grad: bool):
+    """One scale of the STFT-magnitude distance between ``x`` and ``y`` (B, C, T float32 HIP tensors) in one kernel.
+
+    Returns ``(sums, G)``: ``sums`` = 2 float64 on the device, ``sum |p log10 max(|X|, eps) - p log10 max(|Y|, eps)|`` and
+    ``sum | |X| - |Y| |`` over all B C N F elements; ``G`` = ``g_log`` d sums[0]/dX + ``g_mag`` d sums[1]/dX as a complex64
+    tensor of logical shape (B, C, F, N) (the bin-contiguous memory ``stft_adjoint`` reads without a copy), or None
+    without ``want_grad``.  No spectrum is written, nothing is read back to the host."""
+    _require_native_ok(x)
+    _require_native_ok(y)
+    if x.shape != y.shape or x.ndim != 3 or x.dtype != torch.float32 or y.dtype != torch.float32 or x.device != y.device:
+        raise ValueError("stft_distance: two float32 (B, C, T) tensors of one shape on one device")
+    B, C, T = x.shape
+    x, y = x.contiguous(), y.contiguous()
+    dev = x.device
+    lib = _native.lib()
+    nbytes = lib.at_stft_dist_workspace_bytes(B * C, T, n_fft, hop)
+    _native.check(min(nbytes, 0), "at_stft_dist_workspace_bytes")
+    ws = _workspace(nbytes, dev)
+    sums = torch.empty(2, dtype=torch.float64, device=dev)
+    G = None
+    if want_grad:
+        G = _alloc_retry(lambda: torch.empty((B, C, 1 + T // hop, n_fft // 2 + 1), dtype=torch.complex64, device=dev))
+    code = lib.at_stft_dist_f32(_native.ptr(x), _native.ptr(y), B * C, T, _native.ptr(window),
+                                _native.ptr(tables.stft_twiddles(n_fft, dev)), n_fft, hop, clamp_eps, power, g_log, g_mag,
+                                _native.ptr(G), _native.ptr(sums), _native.ptr(ws), ws.numel(), _native.current_stream(dev))
+    _native.check(code, "at_stft_dist_f32")
+    return sums, (None if G is None else G.transpose(2, 3))
+
+
 def istft_adjoint_supported(n_fft: int, hop: int) -> bool:
     return istft_fused_supported(n_fft, hop) and (n_fft // 2) % hop == 0 and stft_fused_supported(n_fft)
 

@@ -3,12 +3,15 @@
 Each scale calls ``AudioSignal.stft`` / ``mel_spectrogram`` on both signals; for HIP tensors that
 require gradients those run the fused forward kernels and their adjoints
 (``spectral._NativeStft`` / ``_NativeStftMel``), so a multi-scale mel loss never materialises a
-spectrum gradient in HBM."""
+spectrum gradient in HBM.  ``MultiScaleSTFTLoss(fused=True)`` goes further: one kernel per scale takes both signals
+to the loss sums and dL/dX (``csrc/stftdist.hip``), no spectrum is written at all."""
 import typing
 
 import numpy as np
+import torch
 from torch import nn
 
+from .. import kernels
 from ..spectral import STFTParams
 
 
@@ -25,22 +28,73 @@ def _log_and_linear(loss_fn, a, b, clamp_eps, power, log_weight, mag_weight):
     return log_weight * loss_fn(la, lb) + mag_weight * loss_fn(a, b)
 
 
+class _StftDistance(torch.autograd.Function):
+    """One scale of the L1 STFT-magnitude distance as ONE kernel (``kernels.stft_distance``): the value from the two
+    signals, and -- only when the estimate needs a gradient -- dL/dX, which backward hands to the native STFT adjoint.
+    Neither spectrum nor any intermediate of the loss exists in memory."""
+
+    @staticmethod
+    def forward(ctx, est, ref, window, n_fft, hop, clamp_eps, power, log_weight, mag_weight):
+        B, C, T = est.shape
+        count = B * C * (1 + T // hop) * (n_fft // 2 + 1)
+        sums, G = kernels.stft_distance(est.detach(), ref.detach(), window, n_fft, hop, clamp_eps, power,
+                                        log_weight / count, mag_weight / count, ctx.needs_input_grad[0])
+        ctx.save_for_backward(G, window)
+        ctx.cfg = (n_fft, hop, T)
+        return (sums[0] * (log_weight / count) + sums[1] * (mag_weight / count)).to(est.dtype)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        G, window = ctx.saved_tensors
+        n_fft, hop, T = ctx.cfg
+        return (kernels.stft_adjoint(G, window, n_fft, hop, T) * grad_out,) + (None,) * 8
+
+
 class MultiScaleSTFTLoss(nn.Module):
     """Multi-resolution STFT magnitude distance (DDSP, Engel et al. 2019; spectral.py:11-94):
     for every window length w (hop w/4) the log-power and the linear magnitudes are compared with
-    ``loss_fn``.  ``weight`` is carried for the trainer, not applied here."""
+    ``loss_fn``.  ``weight`` is carried for the trainer, not applied here.
+
+    ``fused=True`` (not in the reference) evaluates every scale that qualifies with the fused distance kernel: both
+    signals float32 HIP tensors of one shape, ``loss_fn`` an ``nn.L1Loss`` with mean reduction, at most one signal requiring
+    a gradient, a power-of-two window of 32 ... 2048.  Such a scale does NOT touch ``stft_data`` of either signal; every
+    other scale runs the code of ``fused=False``."""
 
     def __init__(self, window_lengths: typing.List[int] = [2048, 512], loss_fn: typing.Callable = nn.L1Loss(),
                  clamp_eps: float = 1e-5, mag_weight: float = 1.0, log_weight: float = 1.0, pow: float = 2.0,
-                 weight: float = 1.0, match_stride: bool = False, window_type: str = None):
+                 weight: float = 1.0, match_stride: bool = False, window_type: str = None, fused: bool = False):
         super().__init__()
         self.stft_params = _scales(window_lengths, match_stride, window_type)
         self.loss_fn, self.clamp_eps, self.pow = loss_fn, clamp_eps, pow
         self.log_weight, self.mag_weight, self.weight = log_weight, mag_weight, weight
+        self.fused = fused
+
+    def _fused_scale(self, x, y, s):
+        """The scale's loss from the fused kernel, or None when the scale does not qualify."""
+        xa, ya = x.audio_data, y.audio_data
+        if not (self.fused and type(self.loss_fn) is nn.L1Loss and self.loss_fn.reduction == "mean"
+                and xa.is_cuda and ya.is_cuda and xa.dtype == ya.dtype == torch.float32 and xa.ndim == 3
+                and xa.shape == ya.shape and xa.device == ya.device):
+            return None
+        grad = torch.is_grad_enabled()
+        gx, gy = grad and xa.requires_grad, grad and ya.requires_grad
+        wtype = s.window_type or x.stft_params.window_type
+        if (gx and gy) or wtype != (s.window_type or y.stft_params.window_type):
+            return None
+        if not kernels.stft_distance_supported(s.window_length, s.hop_length, xa.shape[-1], self.clamp_eps, self.pow):
+            return None
+        est, ref = (ya, xa) if gy else (xa, ya)          # L1 is symmetric: the signal that needs a gradient is the estimate
+        window = x.get_window(wtype, s.window_length, str(xa.device))
+        return _StftDistance.apply(est, ref, window, s.window_length, s.hop_length, float(self.clamp_eps), float(self.pow),
+                                   float(self.log_weight), float(self.mag_weight))
 
     def forward(self, x, y):
         total = 0.0
         for s in self.stft_params:
+            fused = self._fused_scale(x, y, s)
+            if fused is not None:
+                total = total + fused
+                continue
             # as in the reference, match_stride of the scale is NOT forwarded to stft()
             x.stft(s.window_length, s.hop_length, s.window_type)
             y.stft(s.window_length, s.hop_length, s.window_type)

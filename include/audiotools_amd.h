@@ -149,6 +149,26 @@ int at_stft_mel_adjoint_f32(const float* X, const float* gmel, const int* bin_ba
                             int64_t rows, int64_t n_frames, const float* window, const float* twiddles, int n_fft,
                             int hop, float* out, int64_t out_len, void* stream);
 
+/* ---- fused STFT-magnitude distance: loss sums and dL/dX of one scale in one kernel -------------
+ * Replaces, per scale of  audiotools/metrics/spectral.py:11-94  (MultiScaleSTFTLoss with an L1 loss_fn), the two stft()
+ * calls, every element-wise pass over the two spectra and their autograd replay.  With X = STFT(x), Y = STFT(y)
+ * (centre reflect padding of n_fft/2, no outer padding), N = 1 + T/hop frames, F = n_fft/2 + 1 bins, a = |X|, b = |Y|,
+ * p = power, eps = clamp_eps:
+ *   sums[0] = sum |p log10 max(a, eps) - p log10 max(b, eps)|,   sums[1] = sum |a - b|      over rows * N * F elements
+ *   G (rows, N, F) complex64, bin-contiguous (what at_stft_adjoint_f32 reads), or NULL: dL/dX as dRe + i dIm,
+ *     G = (g_mag sgn(a - b) + g_log sgn(max(a, eps) - max(b, eps)) [a >= eps] p / (ln 10 a)) X / a
+ *     exactly 0 where a = 0 (|X|^2 below FLT_MIN), never NaN.  The caller passes g_log = log_weight / (rows N F) and
+ *     g_mag = mag_weight / (rows N F).
+ *   sums      DEVICE, 2 doubles; bit-equal for equal inputs on one device (no atomics)
+ *   workspace at_stft_dist_workspace_bytes(rows, T, n_fft, hop) bytes (a negative error for shapes the kernel does not take)
+ * Power-of-two n_fft in 32 ... 2048 (at_stft_fused_supported), hop == n_fft/4, T > n_fft/2, eps^2 >= FLT_MIN, power > 0:
+ * anything else is AT_ERR_UNSUPPORTED.  NULL x / y / window / twiddles / sums / workspace: AT_ERR_INVALID before any HIP call.
+ */
+int64_t at_stft_dist_workspace_bytes(int64_t rows, int64_t T, int n_fft, int hop);
+int at_stft_dist_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                     int n_fft, int hop, float clamp_eps, float power, float g_log, float g_mag, float* G, double* sums,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- BS.1770 integrated loudness ---------------------------------------------------
  * Replaces  audiotools/core/loudness.py:102-126  (2x torchaudio.functional.lfilter, the
  *           CPU/IIR branch), :164-174 (julius.core.unfold), :176-247 (gated integration).

@@ -1,11 +1,14 @@
 #!/usr/bin/env python
-"""Forward + backward of a magnitude loss through stft(): native kernels vs torch.stft autograd on the GPU."""
+"""Forward + backward of a magnitude loss through stft(): native kernels vs torch.stft autograd on the GPU.
+
+usage: gradbench.py [B [case]]    case: all (default) | stft | mel | dacmel | msstft"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import audiotools_amd as A
 from audiotools_amd import spectral
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 128
+CASE = sys.argv[2] if len(sys.argv) > 2 else "all"
 x = (0.1 * torch.randn(B, 2, 441000, device="cuda")).clamp_(-1, 1)
 
 def run(native):
@@ -26,8 +29,9 @@ def run(native):
     finally:
         spectral._native_autograd_ok = saved
 
-g1 = run(True); g2 = run(False)
-print("grad rel diff", float((g1 - g2).abs().max() / g2.abs().max()))
+if CASE in ("all", "stft"):
+    g1 = run(True); g2 = run(False)
+    print("grad rel diff", float((g1 - g2).abs().max() / g2.abs().max()))
 
 
 def run_mel(native):
@@ -48,8 +52,9 @@ def run_mel(native):
     finally:
         spectral._native_autograd_ok = saved
 
-m1 = run_mel(True); m2 = run_mel(False)
-print("mel grad rel diff", float((m1 - m2).abs().max() / m2.abs().max()))
+if CASE in ("all", "mel"):
+    m1 = run_mel(True); m2 = run_mel(False)
+    print("mel grad rel diff", float((m1 - m2).abs().max() / m2.abs().max()))
 
 
 def run_dac_mel(native):
@@ -74,5 +79,61 @@ def run_dac_mel(native):
     finally:
         spectral._native_autograd_ok = saved
 
-d1 = run_dac_mel(True); d2 = run_dac_mel(False)
-print("7-scale grad rel diff", float((d1 - d2).abs().max() / d2.abs().max()))
+if CASE in ("all", "dacmel"):
+    d1 = run_dac_mel(True); d2 = run_dac_mel(False)
+    print("7-scale grad rel diff", float((d1 - d2).abs().max() / d2.abs().max()))
+
+
+def run_msstft(rounds=5, reps=20):
+    """MultiScaleSTFTLoss at its default scales (2048, 512), estimate vs target of 32 x 2 ch x 10 s each, forward + backward:
+    fused=True (csrc/stftdist.hip) against fused=False, alternating in one process, every window timed with HIP events."""
+    from audiotools_amd import metrics
+    xs, ys = x[:32], (x[32:64] if B >= 64 else x[:32].flip(0)).clone()
+    losses = {f: metrics.spectral.MultiScaleSTFTLoss(fused=f) for f in (False, True)}
+
+    def fn(fused):
+        xa = xs.clone().requires_grad_(True)
+        losses[fused](A.AudioSignal(xa, 44100), A.AudioSignal(ys, 44100)).backward()
+        return xa.grad
+
+    grads = {f: fn(f) for f in (False, True)}          # warm-up of both paths (code objects, allocator, tables)
+    times = {False: [], True: []}
+    for _ in range(rounds):
+        for f in (False, True):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(reps):
+                fn(f)
+            t1.record()
+            t1.synchronize()
+            times[f].append(t0.elapsed_time(t1) / reps)
+    for f in (False, True):
+        ts = sorted(times[f])
+        print(f"MultiScaleSTFTLoss [2048, 512] fwd + bwd, 32x2chx10s, fused={f}: median {ts[len(ts) // 2]:8.2f} ms  "
+              f"(min {ts[0]:.2f}, max {ts[-1]:.2f}; {rounds} windows of {reps})", flush=True)
+    # what the fused path has to move: per scale 2 S in, G out and in (4 S each way, complex64 at hop n/4), ~1 S out
+    S = xs.numel() * 4
+    med = sorted(times[True])[rounds // 2]
+    print(f"fused path: {2 * 11 * S / 1e9:.2f} GB by its byte budget (11 S per scale) -> {2 * 11 * S / med / 1e6:.0f} GB/s end to end")
+    print("fused vs unfused grad rel diff", float((grads[True] - grads[False]).abs().max() / grads[False].abs().max()))
+
+    # the kernel alone (both scales, with and without G)
+    from audiotools_amd import kernels
+    for n_fft in (2048, 512):
+        win = A.AudioSignal.get_window("hann", n_fft, str(xs.device))
+        for want in (True, False):
+            call = lambda: kernels.stft_distance(xs, ys, win, n_fft, n_fft // 4, 1e-5, 2.0, 1e-9, 1e-9, want)
+            call()
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(10):
+                call()
+            t1.record()
+            t1.synchronize()
+            ms = t0.elapsed_time(t1) / 10
+            nbytes = 2 * S + (4 * S if want else 0)
+            print(f"at_stft_dist_f32 n_fft={n_fft} G={want}: {ms:7.3f} ms, {nbytes / ms / 1e6:.0f} GB/s of its {nbytes / 1e9:.2f} GB", flush=True)
+
+
+if CASE in ("all", "msstft"):
+    run_msstft()
