@@ -1,0 +1,460 @@
+// Fused mel-spectrogram distance for gfx950: loss sums and dL/dX of ONE scale in one kernel.
+//
+// Replaces, per scale of  reference audiotools/metrics/spectral.py:97-194  (MelSpectrogramLoss with an L1 loss_fn):
+//   two mel_spectrogram() calls (each writes a full spectrum), clamp / pow / log10 / sub / abs / mean on both mel tensors,
+//   the autograd replay of all of them and the read-back of the saved spectrum in the mel adjoint.
+// The distance is a function of two SIGNALS: the kernel reads x and y once, keeps both mel rows on chip, and the only large
+// object it produces is G = dL/dX (when a gradient is wanted), in the layout at_stft_adjoint_f32 reads.
+//
+// Design (CDNA4), on the wave FFT of fft_wave.h with the work split of stft_dist_kernel (stftdist.hip; the frame loader and
+// the transform below are copies of its two lambdas, arithmetic unchanged):
+//  * M = n_fft/2 complex points, 16 per lane, L = M/16 lanes per frame, FW = 64/L frames per wave; persistent grid, one
+//    contiguous run of frame groups per wave; reflect margins by index arithmetic; the window halved at load;
+//  * y and x frames of a group are loaded together (x in flight during y's transform);
+//  * after a transform every lane writes |.| of its 17 bins IN BIN ORDER into the frame's part of the wave slab (free after
+//    the split; M + 1 floats fit).  Band m of a frame belongs to lane m % L of that frame: at most 8 bands per lane
+//    (n_mels <= n_fft/4).  The owner walks the band's contiguous bin span in ascending bin order, one fmaf per bin, one
+//    accumulator per band; the weights come from the per-bin table (at most two bands per bin) held in LDS.  No prefix sums:
+//    the error of a band is proportional to the band, not to the frame;
+//  * of the target only mel_y and c log2 max(mel_y, eps) of the lane's bands stay in registers (16); X stays in registers;
+//  * the owner adds |log difference| and |mel_x - mel_y| and, with GRAD, writes dL/dmel to a per-wave LDS row of FW x n_mels
+//    floats; every lane then projects it back onto its 17 bins, c[k] = w0 gmel[lo] + w1 gmel[hi], G = c X / |X| with v_rsq_f32
+//    (0 where |X|^2 < FLT_MIN), and G leaves through the slab as 512-byte non-temporal runs;
+//  * two float accumulators per lane over the run, one wave reduction, one partial pair per wave; a one-workgroup kernel adds
+//    the partials in double in a fixed order: no atomics, bit-equal sums and G on every run.
+#include "at_common.h"
+#include "fft_wave.h"
+#include <float.h>
+
+extern "C" int at_stft_fused_supported(int n_fft);
+
+namespace {
+
+constexpr int NW = 4;              // waves per workgroup
+constexpr int MAX_BLOCKS = 1024;   // persistent grid bound the workspace is sized for (2 per CU on 512 CUs)
+constexpr int GM_ROW = 512;        // floats of a wave's dL/dmel row: FW * n_mels <= (64 / L) * (8 L)
+
+struct MelArgs {
+  const float* x;          // (rows, T) estimate
+  const float* y;          // (rows, T) target
+  const float* window;     // (n_fft)
+  const float2* tw;        // (n_fft): (cos, -sin)(2 pi k / n_fft)
+  const int* bin_bands;    // (M + 1): lo | hi << 16
+  const float2* bin_w;     // (M + 1): weights of lo and hi (0 where absent)
+  const int* band_span;    // (n_mels): first bin | count << 16
+  float2* G;               // (rows, n_out, M+1) or null
+  float2* partials;        // (gridDim.x * NW) {sum log, sum mag}
+  int T;
+  int n_out;               // frames per row
+  int hop;
+  int gpr;                 // frame groups per row: ceil(n_out / FW)
+  int64_t total_groups;    // rows * gpr
+  int n_mels;
+  float eps;               // clamp of mel (not of its square)
+  float c_log;             // power * log10(2):  c_log * log2(mel) = power * log10 mel
+  float g_logp;            // g_log * power / ln 10
+  float g_mag;
+  int vec2;                // rows of x and y are 8-byte aligned: float2 loads
+};
+
+// LDS (floats): [NW wave slabs][window, halved: 2M][split twiddles: M][pass-2 twiddles: 16 x 36]   (as stft_dist_kernel)
+//               [bin weights: 2 (M+1)][bin bands: M+1][band spans: M/2][GRAD: NW rows of dL/dmel]
+template <int M>
+constexpr int lds_floats(bool grad) {
+  return NW * 2 * WAVE_LDS_SLOTS + 2 * M + M + 16 * 36 + 3 * (M + 1) + M / 2 + (grad ? NW * GM_ROW : 0);
+}
+
+__device__ __forceinline__ float abs2(float2 z) { return fmaf(z.x, z.x, z.y * z.y); }
+__device__ __forceinline__ float sgnf(float a, float b) { return (a > b ? 1.f : 0.f) - (a < b ? 1.f : 0.f); }
+
+template <int M, bool GRAD>
+__global__ __launch_bounds__(NW * 64, 2) void mel_dist_kernel(const MelArgs A) {
+  using P = Plan<M>;
+  constexpr int L = P::L, FW = P::FW, N = 2 * M, F = M + 1;
+  extern __shared__ __attribute__((aligned(16))) float lds_f[];
+  float* s_win = lds_f + NW * 2 * WAVE_LDS_SLOTS;
+  float2* s_twp = reinterpret_cast<float2*>(s_win + N);
+  float* s_tw2 = s_win + N + M;
+  float2* s_bw = reinterpret_cast<float2*>(s_tw2 + 16 * 36);       // an even number of floats in: 8-byte aligned
+  int* s_bb = reinterpret_cast<int*>(s_tw2 + 16 * 36 + 2 * F);
+  int* s_span = s_bb + F;
+  float* s_gm = reinterpret_cast<float*>(s_span + M / 2);
+  // the factor 1/2 of the split step rides on the window (exact in binary floating point)
+  for (int i = threadIdx.x; i < N; i += NW * 64) s_win[i] = 0.5f * A.window[i];
+  for (int i = threadIdx.x; i < M / 2; i += NW * 64) s_twp[i] = A.tw[i];
+  if constexpr (P::R2 > 1) {
+    for (int i = threadIdx.x; i < 16 * P::R2; i += NW * 64) {
+      const int jj = i / P::R2, r = i % P::R2;
+      reinterpret_cast<float2*>(s_tw2 + jj * 36)[r] = A.tw[r * jj * (N / (16 * P::R2))];
+    }
+  }
+  for (int i = threadIdx.x; i < F; i += NW * 64) {
+    s_bw[i] = A.bin_w[i];
+    s_bb[i] = A.bin_bands[i];
+  }
+  // spans: bands that do not exist are empty; a span never leaves the F bins whatever the table says
+  for (int i = threadIdx.x; i < M / 2; i += NW * 64) {
+    const int sp = i < A.n_mels ? A.band_span[i] : 0;
+    const int k0 = min(sp & 0xffff, F);
+    const int cnt = min((sp >> 16) & 0x7fff, F - k0);
+    s_span[i] = k0 | (cnt << 16);
+  }
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int fs = lane / L;  // frame slot inside the wave
+  const int t = lane % L;   // thread inside the frame
+  float2* wbuf = reinterpret_cast<float2*>(lds_f) + wave * WAVE_LDS_SLOTS;
+  float2* fbuf = wbuf + fs * P::SLOTS;
+  float* fmag = reinterpret_cast<float*>(fbuf);           // |.| of the frame's F bins, in bin order (F <= 2 SLOTS floats)
+  float* grow = s_gm + wave * GM_ROW + fs * A.n_mels;     // dL/dmel of the frame (GRAD only; never touched otherwise)
+
+  constexpr int NB2 = 16 / P::R2;
+  constexpr int NB3 = 16 / P::R3;
+  float2 tw3b[P::R3 > 1 ? NB3 : 1];  // base twiddle per butterfly of pass 3; its powers are derived
+  if constexpr (P::R3 > 1) {
+    constexpr int NS = 16 * P::R2;
+#pragma unroll
+    for (int b = 0; b < NB3; ++b) tw3b[b] = A.tw[((t + b * L) % NS) * (N / (NS * P::R3))];
+  }
+
+  // ---- samples of this thread's frame: points t + L q of z[n] = s[2n] + i s[2n+1].  Interior frames load directly;
+  // a group that touches a reflected margin takes a rolled loop through the wave's slab (index arithmetic, no copy).
+  auto load_frame = [&](float2 (&a)[16], const float* __restrict__ sr, int s0, bool interior) __attribute__((always_inline)) {
+    if (interior) {
+      if (A.vec2) {
+        const float2* __restrict__ p = reinterpret_cast<const float2*>(sr + s0);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) a[q] = p[t + L * q];
+      } else {
+        const float* __restrict__ p = sr + s0;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) a[q] = make_float2(p[2 * (t + L * q)], p[2 * (t + L * q) + 1]);
+      }
+    } else {
+#pragma unroll 1
+      for (int q = 0; q < 16; ++q) {
+        const int n = t + L * q;
+        int u0 = s0 + 2 * n, u1 = u0 + 1;          // centre reflect padding: one reflection (T > n_fft/2)
+        u0 = u0 < 0 ? -u0 : u0; u0 = u0 >= A.T ? 2 * (A.T - 1) - u0 : u0;
+        u1 = u1 < 0 ? -u1 : u1; u1 = u1 >= A.T ? 2 * (A.T - 1) - u1 : u1;
+        u0 = min(max(u0, 0), A.T - 1); u1 = min(max(u1, 0), A.T - 1);
+        fbuf[n] = make_float2(sr[u0], sr[u1]);
+      }
+      wave_sync();
+#pragma unroll
+      for (int q = 0; q < 16; ++q) a[q] = fbuf[t + L * q];
+      wave_sync();
+    }
+  };
+
+  // ---- window, M-point complex FFT, real-FFT split.  Out: bins k = t + L q in xa[q], bins M - k in xb[q] (thread 0,
+  // q = 0: DC and Nyquist), bin M/2 in xh (thread 0 only; 0 elsewhere).  The slab is free again on return.
+  auto transform = [&](float2 (&a)[16], float2 (&xa)[8], float2 (&xb)[8], float2& xh) __attribute__((always_inline)) {
+    {
+      const float2* w2 = reinterpret_cast<const float2*>(s_win);
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const float2 w = w2[t + L * q];
+        a[q] = make_float2(a[q].x * w.x, a[q].y * w.y);
+      }
+    }
+    pass_compute_store<16, 1, L>(a, fbuf, t, nullptr);
+    wave_sync();
+    if constexpr (P::R2 > 1) {
+      load_points<L>(a, fbuf, t);
+      wave_sync();
+      float2 tw2[NB2 * P::R2];
+#pragma unroll
+      for (int b = 0; b < NB2; ++b) {
+        const float2* rowp = reinterpret_cast<const float2*>(s_tw2 + ((t + b * L) & 15) * 36);
+#pragma unroll
+        for (int r = 1; r < P::R2; ++r) tw2[b * P::R2 + r] = rowp[r];
+      }
+      pass_compute_store<P::R2, 16, L>(a, fbuf, t, tw2);
+      wave_sync();
+    }
+    if constexpr (P::R3 > 1) {
+      load_points<L>(a, fbuf, t);
+      wave_sync();
+      float2 tw3[NB3 * P::R3];
+#pragma unroll
+      for (int b = 0; b < NB3; ++b) {
+        tw3[b * P::R3 + 1] = tw3b[b];
+#pragma unroll
+        for (int r = 2; r < P::R3; ++r) tw3[b * P::R3 + r] = cmul(tw3[b * P::R3 + r - 1], tw3b[b]);
+      }
+      pass_compute_store<P::R3, 16 * P::R2, L>(a, fbuf, t, tw3);
+      wave_sync();
+    }
+    float2 zh = make_float2(0.f, 0.f);
+    if (t == 0) zh = fbuf[phys<L>(M / 2)];
+    xh = make_float2(2.f * zh.x, -2.f * zh.y);       // k == M/2: X = conj(Z[M/2])  (Z carries the halved window)
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int k = t + L * q;
+      const float2 zk = fbuf[phys<L>(k)];
+      const float2 zm = fbuf[phys<L>((M - k) & (M - 1))];
+      if (q == 0 && t == 0) {   // packed point 0: DC and Nyquist, two real bins
+        xa[q] = make_float2(2.f * (zk.x + zk.y), 0.f);
+        xb[q] = make_float2(2.f * (zk.x - zk.y), 0.f);
+      } else {
+        const float2 twp = s_twp[k];  // (cos, -sin)(2 pi k / N)
+        const float sr = zk.x + zm.x, si = zk.y - zm.y;
+        const float dr = zk.x - zm.x, di = zk.y + zm.y;
+        const float c = twp.x, s = -twp.y;
+        const float pp = fmaf(s, dr, -c * di);
+        const float qq = fmaf(s, di, c * dr);
+        xa[q] = make_float2(sr - pp, si - qq);
+        xb[q] = make_float2(sr + pp, -si - qq);
+      }
+    }
+    wave_sync();
+  };
+
+  // ---- mel row of the frame from its spectrum: magnitudes through the slab, then the lane's bands m = t + L j.
+  // Summation order of a band: its bins in ascending order, s = fmaf(w, |.|, s) from s = 0 (the four loads of a step are
+  // independent, the adds are not reordered; a slot past the span's end adds w = 0, which leaves s as it is).
+  auto mel_row = [&](const float2 (&xa)[8], const float2 (&xb)[8], float2 xh, float (&mel)[8]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int k = t + L * q;
+      fmag[k] = __builtin_amdgcn_sqrtf(abs2(xa[q]));
+      fmag[M - k] = __builtin_amdgcn_sqrtf(abs2(xb[q]));
+    }
+    if (t == 0) fmag[M / 2] = __builtin_amdgcn_sqrtf(abs2(xh));
+    wave_sync();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int m = t + L * j;                   // < 8 L = M/2: inside the span table
+      const int sp = s_span[m];
+      const int k0 = sp & 0xffff, cnt = sp >> 16;
+      float s = 0.f;
+      for (int i = 0; i < cnt; i += 4) {
+        float w[4], v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int k = min(k0 + i + u, M);
+          const float2 ww = s_bw[k];
+          const float wk = (s_bb[k] & 0xffff) == m ? ww.x : ww.y;
+          w[u] = i + u < cnt ? wk : 0.f;
+          v[u] = fmag[k];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) s = fmaf(w[u], v[u], s);
+      }
+      mel[j] = s;
+    }
+    wave_sync();                                 // the slab is free again
+  };
+
+  // ---- this wave's run of frame groups
+  const int64_t n_waves = (int64_t)gridDim.x * NW;
+  const int64_t gw = (int64_t)blockIdx.x * NW + wave;
+  const int64_t g_lo = A.total_groups * gw / n_waves;
+  const int64_t g_hi = A.total_groups * (gw + 1) / n_waves;
+  float s_log = 0.f, s_mag = 0.f;
+
+  for (int64_t g = g_lo; g < g_hi; ++g) {
+    const int64_t row = g / A.gpr;
+    const int gb = (int)(g - row * A.gpr);
+    const int f0 = gb * FW;
+    const bool valid = f0 + fs < A.n_out;
+    const int fo = min(f0 + fs, A.n_out - 1);     // slots past the row's last frame repeat it (and are masked below)
+    const int s0 = fo * A.hop - M;                // first sample of the frame in un-padded coordinates
+    const bool interior = __all(s0 >= 0 && s0 + N <= A.T);
+    float2 ay[16], ax[16];
+    load_frame(ay, A.y + row * A.T, s0, interior);
+    load_frame(ax, A.x + row * A.T, s0, interior);
+
+    // target: keep mel_y and its log term for the lane's bands
+    float my[8], ly[8];
+    {
+      float2 xa[8], xb[8], xh;
+      transform(ay, xa, xb, xh);
+      mel_row(xa, xb, xh, my);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ly[j] = A.c_log * __builtin_amdgcn_logf(fmaxf(my[j], A.eps));
+    }
+
+    // estimate: X stays in registers until G is formed
+    {
+      float2 xa[8], xb[8], xh;
+      float mx[8];
+      transform(ax, xa, xb, xh);
+      mel_row(xa, xb, xh, mx);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int m = t + L * j;
+        const bool on = valid && m < A.n_mels;
+        const float a = mx[j], b = my[j];
+        const float la = A.c_log * __builtin_amdgcn_logf(fmaxf(a, A.eps));
+        s_log += on ? fabsf(la - ly[j]) : 0.f;
+        s_mag += on ? fabsf(a - b) : 0.f;
+        if constexpr (GRAD) {
+          const float sl = sgnf(fmaxf(a, A.eps), fmaxf(b, A.eps));
+          const float gl = a >= A.eps ? A.g_logp * sl * __builtin_amdgcn_rcpf(a) : 0.f;
+          if (m < A.n_mels) grow[m] = fmaf(A.g_mag, sgnf(a, b), gl);
+        }
+      }
+      if constexpr (GRAD) {
+        wave_sync();
+        // back-projection onto the lane's bins; a slot of weight 0 adds exactly 0 whatever band index it carries
+        auto gbin = [&](float2 X, int k) __attribute__((always_inline)) -> float2 {
+          const float2 w = s_bw[k];
+          const int bb = s_bb[k];
+          const int lo = min(bb & 0xffff, A.n_mels - 1), hi = min((bb >> 16) & 0xffff, A.n_mels - 1);
+          const float c0 = w.x != 0.f ? w.x * grow[lo] : 0.f;
+          const float c = w.y != 0.f ? fmaf(w.y, grow[hi], c0) : c0;
+          // 1/|X|; G = 0 where |X|^2 is zero (or below the normal range, where v_rsq_f32 is not defined)
+          const float a2 = abs2(X);
+          const float inv = a2 >= FLT_MIN ? __builtin_amdgcn_rsqf(a2) : 0.f;
+          const float coef = c * inv;
+          return make_float2(coef * X.x, coef * X.y);
+        };
+        float2* sx = fbuf;                           // G of frame slot fs, bins in order
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const int k = t + L * q;
+          sx[k] = gbin(xa[q], k);
+          sx[M - k] = gbin(xb[q], M - k);
+        }
+        if (t == 0) sx[M / 2] = gbin(xh, M / 2);
+        wave_sync();
+        // the FW frames of the group are consecutive rows of G: (M + 1) FW contiguous float2, streamed as 512-byte runs
+        constexpr int TOT = FW * (M + 1);
+        constexpr int NST = (TOT + 63) / 64;
+        const int tot = min(FW, A.n_out - f0) * (M + 1);       // only the frames that exist
+        float2* __restrict__ obase = A.G + (row * A.n_out + f0) * (M + 1);
+#pragma unroll
+        for (int i = 0; i < NST; ++i) {
+          const int idx = i * 64 + lane;
+          if (idx < tot) {
+            const int f = idx / (M + 1);
+            at::stg2<true>(obase + idx, wbuf[f * P::SLOTS + (idx - f * (M + 1))]);
+          }
+        }
+        wave_sync();
+      }
+    }
+  }
+  s_log = at::wave_sum(s_log);
+  s_mag = at::wave_sum(s_mag);
+  if (lane == 0) A.partials[gw] = make_float2(s_log, s_mag);
+}
+
+// One workgroup: the partial pairs of all waves, added in double in a fixed order (thread i takes i, i + 256, ...; then a
+// fixed tree), so that the same inputs give the same bits on every run.  The scheme of stft_dist_finalize, restated.
+__global__ __launch_bounds__(256) void mel_dist_finalize(const float2* __restrict__ partials, int n, double* __restrict__ sums) {
+  __shared__ double sh[2][256];
+  double s0 = 0.0, s1 = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const float2 p = partials[i];
+    s0 += (double)p.x;
+    s1 += (double)p.y;
+  }
+  sh[0][threadIdx.x] = s0;
+  sh[1][threadIdx.x] = s1;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      sh[0][threadIdx.x] += sh[0][threadIdx.x + o];
+      sh[1][threadIdx.x] += sh[1][threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    sums[0] = sh[0][0];
+    sums[1] = sh[1][0];
+  }
+}
+
+template <int M, bool GRAD>
+int launch_one(const MelArgs& A, int blocks, hipStream_t stream) {
+  auto kern = mel_dist_kernel<M, GRAD>;
+  const size_t bytes = (size_t)lds_floats<M>(GRAD) * 4;   // n_fft 2048 with G: 71948 B, two workgroups per CU
+  if (bytes > 64 * 1024) {
+    const int e = at::allow_big_lds(reinterpret_cast<const void*>(kern));
+    if (e != AT_OK) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NW * 64), bytes, stream, A);
+  AT_LAUNCH_CHECK();
+  return AT_OK;
+}
+
+template <int M>
+int launch_mel(const MelArgs& A, int blocks, hipStream_t stream) {
+  return A.G ? launch_one<M, true>(A, blocks, stream) : launch_one<M, false>(A, blocks, stream);
+}
+
+// AT_OK when the kernel takes the shape
+int mel_shape_check(int64_t rows, int64_t T, int n_fft, int hop, int n_mels) {
+  if (rows <= 0 || T <= 0 || n_fft <= 0 || hop <= 0 || n_mels <= 0) return AT_ERR_INVALID;
+  if (!at_stft_fused_supported(n_fft) || hop * 4 != n_fft || T <= n_fft / 2 || n_mels > n_fft / 4) return AT_ERR_UNSUPPORTED;
+  const int64_t n_out = 1 + T / hop;
+  if (T >= (1LL << 30) || n_out * (n_fft / 2 + 1) >= (1LL << 31)) return AT_ERR_UNSUPPORTED;   // 32-bit sample / bin indices
+  return AT_OK;
+}
+
+int64_t mel_max_blocks(int64_t rows, int64_t T, int n_fft, int hop) {
+  const int FW = 64 / (n_fft / 32);
+  const int64_t gpr = (1 + T / hop + FW - 1) / FW;
+  const int64_t blocks = (rows * gpr + NW - 1) / NW;
+  return blocks < MAX_BLOCKS ? blocks : MAX_BLOCKS;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t at_mel_dist_workspace_bytes(int64_t rows, int64_t T, int n_fft, int hop, int n_mels) {
+  const int e = mel_shape_check(rows, T, n_fft, hop, n_mels);
+  if (e != AT_OK) return e;
+  return mel_max_blocks(rows, T, n_fft, hop) * NW * (int64_t)sizeof(float2);
+}
+
+int at_mel_dist_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                    int n_fft, int hop, const int* bin_bands, const float* bin_w, const int* band_span, int n_mels,
+                    float clamp_eps, float power, float g_log, float g_mag, float* G, double* sums,
+                    void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!x || !y || !window || !twiddles || !bin_bands || !bin_w || !band_span || !sums || !workspace) return AT_ERR_INVALID;
+  const int e = mel_shape_check(rows, T, n_fft, hop, n_mels);
+  if (e != AT_OK) return e;
+  if (!(clamp_eps >= FLT_MIN) || !(power > 0.f)) return AT_ERR_UNSUPPORTED;
+  if (workspace_bytes < at_mel_dist_workspace_bytes(rows, T, n_fft, hop, n_mels)) return AT_ERR_INVALID;
+  const int M = n_fft / 2, FW = 64 / (M / 16);
+  MelArgs A;
+  A.x = x; A.y = y; A.window = window; A.tw = reinterpret_cast<const float2*>(twiddles);
+  A.bin_bands = bin_bands; A.bin_w = reinterpret_cast<const float2*>(bin_w); A.band_span = band_span;
+  A.G = reinterpret_cast<float2*>(G); A.partials = reinterpret_cast<float2*>(workspace);
+  A.T = (int)T; A.n_out = (int)(1 + T / hop); A.hop = hop;
+  A.gpr = (A.n_out + FW - 1) / FW;
+  A.total_groups = rows * A.gpr;
+  A.n_mels = n_mels;
+  A.eps = clamp_eps;
+  A.c_log = (float)((double)power * 0.30102999566398119521);
+  A.g_logp = (float)((double)g_log * (double)power / 2.30258509299404568402);
+  A.g_mag = g_mag;
+  A.vec2 = ((T % 2) == 0 && (reinterpret_cast<uintptr_t>(x) % 8) == 0 && (reinterpret_cast<uintptr_t>(y) % 8) == 0) ? 1 : 0;
+  int64_t blocks = mel_max_blocks(rows, T, n_fft, hop);
+  const int64_t resident = 2 * (int64_t)at::device_cu_count();      // two workgroups per CU (launch bounds; <= 72 KB of LDS each)
+  if (blocks > resident) blocks = resident;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  int r = AT_ERR_UNSUPPORTED;
+  switch (M) {
+    case 16: r = launch_mel<16>(A, (int)blocks, s); break;
+    case 32: r = launch_mel<32>(A, (int)blocks, s); break;
+    case 64: r = launch_mel<64>(A, (int)blocks, s); break;
+    case 128: r = launch_mel<128>(A, (int)blocks, s); break;
+    case 256: r = launch_mel<256>(A, (int)blocks, s); break;
+    case 512: r = launch_mel<512>(A, (int)blocks, s); break;
+    case 1024: r = launch_mel<1024>(A, (int)blocks, s); break;
+  }
+  if (r != AT_OK) return r;
+  hipLaunchKernelGGL(mel_dist_finalize, dim3(1), dim3(256), 0, s, A.partials, (int)blocks * NW, sums);
+  AT_LAUNCH_CHECK();
+  return AT_OK;
+}
+
+}  // extern "C"

@@ -648,6 +648,49 @@ def stft_distance(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_fft:
     return sums, (None if G is None else G.transpose(2, 3))
 
 
+def mel_distance_supported(n_fft: int, hop: int, T: int, n_mels: int, clamp_eps: float, power: float) -> bool:
+    """The fused mel distance kernel (csrc/meldist.hip) takes this scale: the shapes of :func:`stft_distance_supported`,
+    1 <= n_mels <= n_fft / 4, a clamp (applied to mel, not to its square) that is a normal float32, a positive exponent."""
+    return (stft_fused_supported(n_fft) and hop * 4 == n_fft and T > n_fft // 2 and T < 2 ** 30
+            and (1 + T // hop) * (n_fft // 2 + 1) < 2 ** 31 and 1 <= n_mels <= n_fft // 4
+            and float(clamp_eps) >= float(torch.finfo(torch.float32).tiny) and power > 0)
+
+
+def mel_distance(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_fft: int, hop: int, mel_tables, n_mels: int,
+                 clamp_eps: float, power: float, g_log: float, g_mag: float, want_grad: bool):
+    """One scale of the mel-spectrogram distance between ``x`` and ``y`` (B, C, T float32 HIP tensors) in one kernel;
+    ``mel_tables`` = ``tables.mel_dist_tables(...)``.
+
+    Returns ``(sums, G)``: ``sums`` = 2 float64 on the device, ``sum |p log10 max(mel_x, eps) - p log10 max(mel_y, eps)|``
+    and ``sum |mel_x - mel_y|`` over all B C N n_mels elements; ``G`` = ``g_log`` d sums[0]/dX + ``g_mag`` d sums[1]/dX as a
+    complex64 tensor of logical shape (B, C, F, N) (the bin-contiguous memory ``stft_adjoint`` reads without a copy), or
+    None without ``want_grad``.  No spectrum and no mel tensor is written, nothing is read back to the host."""
+    _require_native_ok(x)
+    _require_native_ok(y)
+    if x.shape != y.shape or x.ndim != 3 or x.dtype != torch.float32 or y.dtype != torch.float32 or x.device != y.device:
+        raise ValueError("mel_distance: two float32 (B, C, T) tensors of one shape on one device")
+    B, C, T = x.shape
+    x, y = x.contiguous(), y.contiguous()
+    dev = x.device
+    bands, w, spans = mel_tables
+    if bands.numel() != n_fft // 2 + 1 or w.numel() != 2 * bands.numel() or spans.numel() != n_mels:
+        raise ValueError("mel_distance: tables of another filterbank")
+    lib = _native.lib()
+    nbytes = lib.at_mel_dist_workspace_bytes(B * C, T, n_fft, hop, n_mels)
+    _native.check(min(nbytes, 0), "at_mel_dist_workspace_bytes")
+    ws = _workspace(nbytes, dev)
+    sums = torch.empty(2, dtype=torch.float64, device=dev)
+    G = None
+    if want_grad:
+        G = _alloc_retry(lambda: torch.empty((B, C, 1 + T // hop, n_fft // 2 + 1), dtype=torch.complex64, device=dev))
+    code = lib.at_mel_dist_f32(_native.ptr(x), _native.ptr(y), B * C, T, _native.ptr(window),
+                               _native.ptr(tables.stft_twiddles(n_fft, dev)), n_fft, hop, _native.ptr(bands), _native.ptr(w),
+                               _native.ptr(spans), n_mels, clamp_eps, power, g_log, g_mag, _native.ptr(G), _native.ptr(sums),
+                               _native.ptr(ws), ws.numel(), _native.current_stream(dev))
+    _native.check(code, "at_mel_dist_f32")
+    return sums, (None if G is None else G.transpose(2, 3))
+
+
 def istft_adjoint_supported(n_fft: int, hop: int) -> bool:
     return istft_fused_supported(n_fft, hop) and (n_fft // 2) % hop == 0 and stft_fused_supported(n_fft)
 

@@ -4,14 +4,15 @@ Each scale calls ``AudioSignal.stft`` / ``mel_spectrogram`` on both signals; for
 require gradients those run the fused forward kernels and their adjoints
 (``spectral._NativeStft`` / ``_NativeStftMel``), so a multi-scale mel loss never materialises a
 spectrum gradient in HBM.  ``MultiScaleSTFTLoss(fused=True)`` goes further: one kernel per scale takes both signals
-to the loss sums and dL/dX (``csrc/stftdist.hip``), no spectrum is written at all."""
+to the loss sums and dL/dX (``csrc/stftdist.hip``), no spectrum is written at all; ``MelSpectrogramLoss(fused=True)`` is
+the same for the mel distance (``csrc/meldist.hip``)."""
 import typing
 
 import numpy as np
 import torch
 from torch import nn
 
-from .. import kernels
+from .. import kernels, tables
 from ..spectral import STFTParams
 
 
@@ -103,25 +104,79 @@ class MultiScaleSTFTLoss(nn.Module):
         return total
 
 
+class _MelDistance(torch.autograd.Function):
+    """One scale of the L1 mel-spectrogram distance as ONE kernel (``kernels.mel_distance``): the value from the two
+    signals, and -- only when the estimate needs a gradient -- dL/dX, which backward hands to the native STFT adjoint.
+    Neither spectrum, neither mel tensor nor any intermediate of the loss exists in memory."""
+
+    @staticmethod
+    def forward(ctx, est, ref, window, n_fft, hop, mel_tables, n_mels, clamp_eps, power, log_weight, mag_weight):
+        B, C, T = est.shape
+        count = B * C * (1 + T // hop) * n_mels
+        sums, G = kernels.mel_distance(est.detach(), ref.detach(), window, n_fft, hop, mel_tables, n_mels, clamp_eps, power,
+                                       log_weight / count, mag_weight / count, ctx.needs_input_grad[0])
+        ctx.save_for_backward(G, window)
+        ctx.cfg = (n_fft, hop, T)
+        return (sums[0] * (log_weight / count) + sums[1] * (mag_weight / count)).to(est.dtype)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        G, window = ctx.saved_tensors
+        n_fft, hop, T = ctx.cfg
+        return (kernels.stft_adjoint(G, window, n_fft, hop, T) * grad_out,) + (None,) * 10
+
+
 class MelSpectrogramLoss(nn.Module):
     """Multi-resolution mel-spectrogram distance (spectral.py:97-194): scale i uses
     ``n_mels[i]`` bands between ``mel_fmin[i]`` and ``mel_fmax[i]`` on a window of
-    ``window_lengths[i]`` (hop = window / 4)."""
+    ``window_lengths[i]`` (hop = window / 4).
+
+    ``fused=True`` (not in the reference) evaluates every scale that qualifies with the fused mel distance kernel: both
+    signals float32 HIP tensors of one shape and sample rate, ``loss_fn`` an ``nn.L1Loss`` with mean reduction, at most one
+    signal requiring a gradient, a power-of-two window of 32 ... 2048 and at most window / 4 bands.  Such a scale does NOT
+    touch ``stft_data`` of either signal; every other scale runs the code of ``fused=False``."""
 
     def __init__(self, n_mels: typing.List[int] = [150, 80], window_lengths: typing.List[int] = [2048, 512],
                  loss_fn: typing.Callable = nn.L1Loss(), clamp_eps: float = 1e-5, mag_weight: float = 1.0,
                  log_weight: float = 1.0, pow: float = 2.0, weight: float = 1.0, match_stride: bool = False,
                  mel_fmin: typing.List[float] = [0.0, 0.0], mel_fmax: typing.List[float] = [None, None],
-                 window_type: str = None):
+                 window_type: str = None, fused: bool = False):
         super().__init__()
         self.stft_params = _scales(window_lengths, match_stride, window_type)
         self.n_mels, self.mel_fmin, self.mel_fmax = n_mels, mel_fmin, mel_fmax
         self.loss_fn, self.clamp_eps, self.pow = loss_fn, clamp_eps, pow
         self.log_weight, self.mag_weight, self.weight = log_weight, mag_weight, weight
+        self.fused = fused
+
+    def _fused_scale(self, x, y, s, n_mels, fmin, fmax):
+        """The scale's loss from the fused kernel, or None when the scale does not qualify."""
+        xa, ya = x.audio_data, y.audio_data
+        if not (self.fused and type(self.loss_fn) is nn.L1Loss and self.loss_fn.reduction == "mean"
+                and xa.is_cuda and ya.is_cuda and xa.dtype == ya.dtype == torch.float32 and xa.ndim == 3
+                and xa.shape == ya.shape and xa.device == ya.device and x.sample_rate == y.sample_rate):
+            return None
+        grad = torch.is_grad_enabled()
+        gx, gy = grad and xa.requires_grad, grad and ya.requires_grad
+        wtype = s.window_type or x.stft_params.window_type
+        if (gx and gy) or wtype != (s.window_type or y.stft_params.window_type):
+            return None
+        if not kernels.mel_distance_supported(s.window_length, s.hop_length, xa.shape[-1], n_mels, self.clamp_eps, self.pow):
+            return None
+        mel_tables = tables.mel_dist_tables(x.sample_rate, s.window_length, n_mels, fmin, fmax, xa.device)
+        if mel_tables is None:
+            return None
+        est, ref = (ya, xa) if gy else (xa, ya)          # L1 is symmetric: the signal that needs a gradient is the estimate
+        window = x.get_window(wtype, s.window_length, str(xa.device))
+        return _MelDistance.apply(est, ref, window, s.window_length, s.hop_length, mel_tables, n_mels, float(self.clamp_eps),
+                                  float(self.pow), float(self.log_weight), float(self.mag_weight))
 
     def forward(self, x, y):
         total = 0.0
         for n_mels, fmin, fmax, s in zip(self.n_mels, self.mel_fmin, self.mel_fmax, self.stft_params):
+            fused = self._fused_scale(x, y, s, n_mels, fmin, fmax) if self.fused else None
+            if fused is not None:
+                total = total + fused
+                continue
             kw = dict(window_length=s.window_length, hop_length=s.hop_length, window_type=s.window_type)
             mx = x.mel_spectrogram(n_mels, mel_fmin=fmin, mel_fmax=fmax, **kw)
             my = y.mel_spectrogram(n_mels, mel_fmin=fmin, mel_fmax=fmax, **kw)

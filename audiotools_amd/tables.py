@@ -312,6 +312,37 @@ def mel_bin_table(sr, n_fft, n_mels, fmin, fmax, device):
     return device_table(key, device, lambda: t)
 
 
+def mel_band_spans_np(basis: np.ndarray):
+    """Per-band view of a triangular filterbank for the fused mel distance kernel: the non-zero bins of a band are one
+    contiguous run.  Returns ``spans int32 (n_mels,) = first bin | count << 16`` (count 0 for an all-zero band), or None
+    when some band's non-zero bins are not contiguous or :func:`mel_bin_table_np` has no table for the basis."""
+    if mel_bin_table_np(basis) is None:
+        return None
+    spans = np.zeros(basis.shape[0], dtype=np.int32)
+    for m, row in enumerate(basis):
+        nz = np.nonzero(row)[0]
+        if len(nz) == 0:
+            continue
+        if nz[-1] - nz[0] + 1 != len(nz):
+            return None
+        spans[m] = int(nz[0]) | len(nz) << 16
+    return spans
+
+
+def mel_dist_tables(sr, n_fft, n_mels, fmin, fmax, device):
+    """Device tables of the fused mel distance (cached): ``(bands, weights, spans)`` = :func:`mel_bin_table` plus
+    :func:`mel_band_spans_np`, or None when the filterbank has no such form."""
+    key = ("mel_spans", sr, n_fft, n_mels, fmin, fmax)
+    if key in _mel_units_unsupported:
+        return None
+    bins = mel_bin_table(sr, n_fft, n_mels, fmin, fmax, device)
+    spans = None if bins is None else mel_band_spans_np(mel_filters_np(sr, n_fft, n_mels, fmin, fmax))
+    if spans is None:
+        _mel_units_unsupported.add(key)
+        return None
+    return tuple(bins) + (device_table(key, device, lambda: spans),)
+
+
 _mel_units_unsupported = set()
 
 

@@ -169,6 +169,32 @@ int at_stft_dist_f32(const float* x, const float* y, int64_t rows, int64_t T, co
                      int n_fft, int hop, float clamp_eps, float power, float g_log, float g_mag, float* G, double* sums,
                      void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- fused mel-spectrogram distance: loss sums and dL/dX of one scale in one kernel ---------------
+ * Replaces, per scale of  audiotools/metrics/spectral.py:97-194  (MelSpectrogramLoss with an L1 loss_fn), the two
+ * mel_spectrogram() calls, every element-wise pass over the two mel tensors, their autograd replay and the read-back of the
+ * saved spectrum.  With X = STFT(x), Y = STFT(y) as for at_stft_dist_f32, mel_x[f,m] = sum_k basis[m,k] |X[f,k]| (the bins of
+ * a band added in ascending order), mel_y likewise, N = 1 + T/hop frames, p = power, eps = clamp_eps:
+ *   sums[0] = sum |p log10 max(mel_x, eps) - p log10 max(mel_y, eps)|,   sums[1] = sum |mel_x - mel_y|
+ *     over rows * N * n_mels elements.  The clamp is applied to mel, NOT to its square.
+ *   G (rows, N, n_fft/2+1) complex64, bin-contiguous (what at_stft_adjoint_f32 reads), or NULL: dL/dX,
+ *     gmel[f,m] = g_mag sgn(mel_x - mel_y) + g_log sgn(max(mel_x, eps) - max(mel_y, eps)) [mel_x >= eps] p / (ln 10 mel_x)
+ *     G[f,k]    = (sum_m basis[m,k] gmel[f,m]) X[f,k] / |X[f,k]|       exactly 0 where |X|^2 < FLT_MIN, never NaN.
+ *     The caller passes g_log = log_weight / (rows N n_mels) and g_mag = mag_weight / (rows N n_mels).
+ *   bin_bands (n_fft/2+1) i32 = lo | hi << 16 and bin_w (n_fft/2+1, 2) f32: as for at_stft_mel_adjoint_f32; a slot of
+ *     weight 0 contributes exactly 0 whatever band index it carries
+ *   band_span (n_mels) i32 = first bin | count << 16: the contiguous non-zero bins of every band (count 0: all-zero band)
+ *   sums      DEVICE, 2 doubles; sums and G are bit-equal for equal inputs on one device (no atomics)
+ *   workspace at_mel_dist_workspace_bytes(rows, T, n_fft, hop, n_mels) bytes (a negative error for unsupported shapes)
+ * Power-of-two n_fft in 32 ... 2048, hop == n_fft/4, T > n_fft/2 (index limits of at_stft_dist_f32), 1 <= n_mels <= n_fft/4,
+ * eps >= FLT_MIN, power > 0: anything else is AT_ERR_UNSUPPORTED.  NULL x / y / window / twiddles / tables / sums /
+ * workspace or a short workspace: AT_ERR_INVALID before any HIP call.
+ */
+int64_t at_mel_dist_workspace_bytes(int64_t rows, int64_t T, int n_fft, int hop, int n_mels);
+int at_mel_dist_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                    int n_fft, int hop, const int* bin_bands, const float* bin_w, const int* band_span, int n_mels,
+                    float clamp_eps, float power, float g_log, float g_mag, float* G, double* sums,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- BS.1770 integrated loudness ---------------------------------------------------
  * Replaces  audiotools/core/loudness.py:102-126  (2x torchaudio.functional.lfilter, the
  *           CPU/IIR branch), :164-174 (julius.core.unfold), :176-247 (gated integration).

@@ -84,6 +84,58 @@ if CASE in ("all", "dacmel"):
     print("7-scale grad rel diff", float((d1 - d2).abs().max() / d2.abs().max()))
 
 
+def run_dac_mel_fused(rounds=5, reps=10):
+    """The same 7-scale loss, forward + backward: fused=True (csrc/meldist.hip) against fused=False, alternating in one
+    process, every window timed with HIP events; then the kernel alone per scale, with and without G."""
+    from audiotools_amd import kernels, metrics, tables
+    mels, wins = [5, 10, 20, 40, 80, 160, 320], [32, 64, 128, 256, 512, 1024, 2048]
+    xs, ys = x[:32], (x[32:64] if B >= 64 else x[:32].flip(0)).clone()
+    losses = {f: metrics.spectral.MelSpectrogramLoss(n_mels=mels, window_lengths=wins, mel_fmin=[0] * 7, mel_fmax=[None] * 7,
+                                                     pow=1.0, mag_weight=0.0, fused=f) for f in (False, True)}
+
+    def fn(fused):
+        xa = xs.clone().requires_grad_(True)
+        losses[fused](A.AudioSignal(xa, 44100), A.AudioSignal(ys, 44100)).backward()
+        return xa.grad
+
+    grads = {f: fn(f) for f in (False, True)}          # warm-up of both paths (code objects, allocator, tables)
+    times = {False: [], True: []}
+    for _ in range(rounds):
+        for f in (False, True):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(reps):
+                fn(f)
+            t1.record()
+            t1.synchronize()
+            times[f].append(t0.elapsed_time(t1) / reps)
+    for f in (False, True):
+        ts = sorted(times[f])
+        print(f"7-scale MelSpectrogramLoss fwd + bwd, 32x2chx10s, fused={f}: median {ts[len(ts) // 2]:8.2f} ms  "
+              f"(min {ts[0]:.2f}, max {ts[-1]:.2f}; {rounds} windows of {reps})", flush=True)
+    print("fused vs unfused grad rel diff", float((grads[True] - grads[False]).abs().max() / grads[False].abs().max()))
+    S = xs.numel() * 4
+    for n_mels, n_fft in zip(mels, wins):
+        win = A.AudioSignal.get_window("hann", n_fft, str(xs.device))
+        tb = tables.mel_dist_tables(44100, n_fft, n_mels, 0, None, xs.device)
+        for want in (True, False):
+            call = lambda: kernels.mel_distance(xs, ys, win, n_fft, n_fft // 4, tb, n_mels, 1e-5, 1.0, 1e-9, 0.0, want)
+            call()
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(10):
+                call()
+            t1.record()
+            t1.synchronize()
+            ms = t0.elapsed_time(t1) / 10
+            nbytes = 2 * S + (4 * S if want else 0)
+            print(f"at_mel_dist_f32 n_fft={n_fft} n_mels={n_mels} G={want}: {ms:7.3f} ms, {nbytes / ms / 1e6:.0f} GB/s of its {nbytes / 1e9:.2f} GB", flush=True)
+
+
+if CASE in ("all", "dacmel"):
+    run_dac_mel_fused()
+
+
 def run_msstft(rounds=5, reps=20):
     """MultiScaleSTFTLoss at its default scales (2048, 512), estimate vs target of 32 x 2 ch x 10 s each, forward + backward:
     fused=True (csrc/stftdist.hip) against fused=False, alternating in one process, every window timed with HIP events."""
