@@ -31,7 +31,7 @@ class NativeError(RuntimeError):
     """Raised when the HIP library is unavailable or an entry point fails."""
 
 
-HEADERS = ["at_common.h", "fft_wave.h", "generic_fft.h"]
+HEADERS = ["at_common.h", "fft_wave.h", "generic_fft.h", "dist_ola.h"]
 # per-source extra flags.  The SLP vectoriser turns the float2 butterflies into v_pk_*_f32, which issue
 # at half rate on gfx950 (no throughput gain) and cost v_mov's to build the operand pairs; scalar
 # code is shorter AND needs fewer registers (DESIGN.md 5.1).  Measured, same box, packed -> scalar:
@@ -149,7 +149,11 @@ SIGNATURES = {
     "at_stft_mel_adjoint_f32": (_i32, [_p, _p, _p, _p, _i32, _i64, _i64, _p, _p, _i32, _i32, _p, _i64, _p]),
     "at_stft_dist_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
     "at_stft_dist_f32": (_i32, [_p, _p, _i64, _i64, _p, _p, _i32, _i32, _f32, _f32, _f32, _f32, _p, _p, _p, _i64, _p]),
+    "at_stft_dist_dx_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
+    "at_stft_dist_dx_f32": (_i32, [_p, _p, _i64, _i64, _p, _p, _i32, _i32, _f32, _f32, _f32, _f32, _p, _p, _p, _i64, _p]),
     "at_mel_dist_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32]),
+    "at_mel_dist_dx_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32]),
+    "at_mel_dist_dx_f32": (_i32, [_p, _p, _i64, _i64, _p, _p, _i32, _i32, _p, _p, _p, _i32, _f32, _f32, _f32, _f32, _p, _p, _p, _i64, _p]),
     "at_mel_dist_f32": (_i32, [_p, _p, _i64, _i64, _p, _p, _i32, _i32, _p, _p, _p, _i32, _f32, _f32, _f32, _f32, _p, _p, _p, _i64, _p]),
     "at_fir_per_item_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i32, _i32, _i32, _i32, _p, _p]),
     "at_sinc_taps_f32": (_i32, [_p, _i64, _f32, _i32, _i32, _p, _p]),

@@ -21,9 +21,12 @@
 //    floats; every lane then projects it back onto its 17 bins, c[k] = w0 gmel[lo] + w1 gmel[hi], G = c X / |X| with v_rsq_f32
 //    (0 where |X|^2 < FLT_MIN), and G leaves through the slab as 512-byte non-temporal runs;
 //  * two float accumulators per lane over the run, one wave reduction, one partial pair per wave; a one-workgroup kernel adds
-//    the partials in double in a fixed order: no atomics, bit-equal sums and G on every run.
+//    the partials in double in a fixed order: no atomics, bit-equal sums and G on every run;
+//  * MODE: DIST_NONE (sums), DIST_G (sums and G, above), DIST_DX (sums and the gradient of the SIGNAL: G stays in the slab and
+//    goes through the adjoint transform and the in-wave overlap-add of dist_ola.h; at_mel_dist_dx_f32).
 #include "at_common.h"
 #include "fft_wave.h"
+#include "dist_ola.h"
 #include <float.h>
 
 extern "C" int at_stft_fused_supported(int n_fft);
@@ -55,20 +58,24 @@ struct MelArgs {
   float g_logp;            // g_log * power / ln 10
   float g_mag;
   int vec2;                // rows of x and y are 8-byte aligned: float2 loads
+  OlaOut ola;              // DIST_DX only: where the waveform gradient goes (dist_ola.h)
 };
 
 // LDS (floats): [NW wave slabs][window, halved: 2M][split twiddles: M][pass-2 twiddles: 16 x 36]   (as stft_dist_kernel)
 //               [bin weights: 2 (M+1)][bin bands: M+1][band spans: M/2][GRAD: NW rows of dL/dmel]
+//               [DIST_DX: NW carries of the overlap-add, 24 L floats each]
 template <int M>
-constexpr int lds_floats(bool grad) {
-  return NW * 2 * WAVE_LDS_SLOTS + 2 * M + M + 16 * 36 + 3 * (M + 1) + M / 2 + (grad ? NW * GM_ROW : 0);
+constexpr int lds_floats(int mode) {
+  return NW * 2 * WAVE_LDS_SLOTS + 2 * M + M + 16 * 36 + 3 * (M + 1) + M / 2 + (mode != DIST_NONE ? NW * GM_ROW : 0) +
+         (mode == DIST_DX ? NW * ola_carry_floats<M>() : 0);
 }
 
 __device__ __forceinline__ float abs2(float2 z) { return fmaf(z.x, z.x, z.y * z.y); }
 __device__ __forceinline__ float sgnf(float a, float b) { return (a > b ? 1.f : 0.f) - (a < b ? 1.f : 0.f); }
 
-template <int M, bool GRAD>
+template <int M, int MODE>
 __global__ __launch_bounds__(NW * 64, 2) void mel_dist_kernel(const MelArgs A) {
+  constexpr bool GRAD = MODE != DIST_NONE;
   using P = Plan<M>;
   constexpr int L = P::L, FW = P::FW, N = 2 * M, F = M + 1;
   extern __shared__ __attribute__((aligned(16))) float lds_f[];
@@ -109,6 +116,10 @@ __global__ __launch_bounds__(NW * 64, 2) void mel_dist_kernel(const MelArgs A) {
   float2* fbuf = wbuf + fs * P::SLOTS;
   float* fmag = reinterpret_cast<float*>(fbuf);           // |.| of the frame's F bins, in bin order (F <= 2 SLOTS floats)
   float* grow = s_gm + wave * GM_ROW + fs * A.n_mels;     // dL/dmel of the frame (GRAD only; never touched otherwise)
+  float* carry = s_gm + NW * GM_ROW + wave * ola_carry_floats<M>();   // DIST_DX only: lane-private, element i is lane i % 64's
+  if constexpr (MODE == DIST_DX) {
+    for (int i = lane; i < ola_carry_floats<M>(); i += 64) carry[i] = 0.f;
+  }
 
   constexpr int NB2 = 16 / P::R2;
   constexpr int NB3 = 16 / P::R3;
@@ -250,10 +261,14 @@ __global__ __launch_bounds__(NW * 64, 2) void mel_dist_kernel(const MelArgs A) {
   };
 
   // ---- this wave's run of frame groups
-  const int64_t n_waves = (int64_t)gridDim.x * NW;
+  // (DIST_DX: only the first n_active <= total_groups waves own groups, so that no run is empty)
+  const int64_t n_waves = MODE == DIST_DX ? (int64_t)A.ola.n_active : (int64_t)gridDim.x * NW;
   const int64_t gw = (int64_t)blockIdx.x * NW + wave;
-  const int64_t g_lo = A.total_groups * gw / n_waves;
-  const int64_t g_hi = A.total_groups * (gw + 1) / n_waves;
+  int64_t g_lo = A.total_groups * gw / n_waves;
+  int64_t g_hi = A.total_groups * (gw + 1) / n_waves;
+  if constexpr (MODE == DIST_DX) {
+    if (gw >= n_waves) g_lo = g_hi = 0;
+  }
   float s_log = 0.f, s_mag = 0.f;
 
   for (int64_t g = g_lo; g < g_hi; ++g) {
@@ -322,6 +337,13 @@ __global__ __launch_bounds__(NW * 64, 2) void mel_dist_kernel(const MelArgs A) {
         }
         if (t == 0) sx[M / 2] = gbin(xh, M / 2);
         wave_sync();
+      }
+      if constexpr (MODE == DIST_DX) {
+        // G stays on chip: adjoint transform of every frame, overlap-add inside the wave (dist_ola.h)
+        ola_frame<M>(fbuf, wbuf, s_win, s_twp, s_tw2, tw3b, t, fs, valid);
+        ola_group<M>(reinterpret_cast<const float*>(wbuf), carry, lane, A.ola, row, f0, gb == A.gpr - 1);
+      }
+      if constexpr (MODE == DIST_G) {
         // the FW frames of the group are consecutive rows of G: (M + 1) FW contiguous float2, streamed as 512-byte runs
         constexpr int TOT = FW * (M + 1);
         constexpr int NST = (TOT + 63) / 64;
@@ -337,6 +359,11 @@ __global__ __launch_bounds__(NW * 64, 2) void mel_dist_kernel(const MelArgs A) {
         }
         wave_sync();
       }
+    }
+  }
+  if constexpr (MODE == DIST_DX) {
+    if (g_hi > g_lo && g_hi % A.gpr != 0) {     // the run ends inside a row: its carry is the next wave's missing part
+      for (int i = lane; i < ola_carry_floats<M>(); i += 64) A.ola.seams[gw * ola_carry_floats<M>() + i] = carry[i];
     }
   }
   s_log = at::wave_sum(s_log);
@@ -370,10 +397,11 @@ __global__ __launch_bounds__(256) void mel_dist_finalize(const float2* __restric
   }
 }
 
-template <int M, bool GRAD>
+template <int M, int MODE>
 int launch_one(const MelArgs& A, int blocks, hipStream_t stream) {
-  auto kern = mel_dist_kernel<M, GRAD>;
-  const size_t bytes = (size_t)lds_floats<M>(GRAD) * 4;   // n_fft 2048 with G: 71948 B, two workgroups per CU
+  auto kern = mel_dist_kernel<M, MODE>;
+  // n_fft 2048: 71948 B with G (two workgroups per CU), 96524 B in waveform mode (one workgroup per CU)
+  const size_t bytes = (size_t)lds_floats<M>(MODE) * 4;
   if (bytes > 64 * 1024) {
     const int e = at::allow_big_lds(reinterpret_cast<const void*>(kern));
     if (e != AT_OK) return e;
@@ -385,7 +413,8 @@ int launch_one(const MelArgs& A, int blocks, hipStream_t stream) {
 
 template <int M>
 int launch_mel(const MelArgs& A, int blocks, hipStream_t stream) {
-  return A.G ? launch_one<M, true>(A, blocks, stream) : launch_one<M, false>(A, blocks, stream);
+  if (A.ola.dx) return launch_one<M, DIST_DX>(A, blocks, stream);
+  return A.G ? launch_one<M, DIST_G>(A, blocks, stream) : launch_one<M, DIST_NONE>(A, blocks, stream);
 }
 
 // AT_OK when the kernel takes the shape
@@ -402,6 +431,69 @@ int64_t mel_max_blocks(int64_t rows, int64_t T, int n_fft, int hop) {
   const int64_t gpr = (1 + T / hop + FW - 1) / FW;
   const int64_t blocks = (rows * gpr + NW - 1) / NW;
   return blocks < MAX_BLOCKS ? blocks : MAX_BLOCKS;
+}
+
+// resident workgroups of the persistent grid: two per CU (launch bounds; <= 72 KB of LDS each) -- one where the carries of
+// the waveform mode take the workgroup to 94 KB (n_fft 2048)
+int64_t mel_resident(int n_fft, bool dx) { return (dx && n_fft == 2048 ? 1 : 2) * (int64_t)at::device_cu_count(); }
+
+int64_t dx_max_blocks(int64_t rows, int64_t T, int n_fft, int hop) {
+  const int64_t blocks = mel_max_blocks(rows, T, n_fft, hop), resident = mel_resident(n_fft, true);
+  return blocks < resident ? blocks : resident;
+}
+
+// G != null: dL/dX; dx != null: dL/dx through the overlap-add tail (workspace: partials, seam slots, margins)
+int mel_run(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles, int n_fft,
+            int hop, const int* bin_bands, const float* bin_w, const int* band_span, int n_mels, float clamp_eps, float power,
+            float g_log, float g_mag, float* G, float* dx, double* sums, void* workspace, hipStream_t s) {
+  const int M = n_fft / 2, FW = 64 / (M / 16);
+  MelArgs A;
+  A.x = x; A.y = y; A.window = window; A.tw = reinterpret_cast<const float2*>(twiddles);
+  A.bin_bands = bin_bands; A.bin_w = reinterpret_cast<const float2*>(bin_w); A.band_span = band_span;
+  A.G = reinterpret_cast<float2*>(G); A.partials = reinterpret_cast<float2*>(workspace);
+  A.T = (int)T; A.n_out = (int)(1 + T / hop); A.hop = hop;
+  A.gpr = (A.n_out + FW - 1) / FW;
+  A.total_groups = rows * A.gpr;
+  A.n_mels = n_mels;
+  A.eps = clamp_eps;
+  A.c_log = (float)((double)power * 0.30102999566398119521);
+  A.g_logp = (float)((double)g_log * (double)power / 2.30258509299404568402);
+  A.g_mag = g_mag;
+  A.vec2 = ((T % 2) == 0 && (reinterpret_cast<uintptr_t>(x) % 8) == 0 && (reinterpret_cast<uintptr_t>(y) % 8) == 0) ? 1 : 0;
+  int64_t blocks = mel_max_blocks(rows, T, n_fft, hop);
+  const int64_t resident = mel_resident(n_fft, dx != nullptr);
+  if (blocks > resident) blocks = resident;
+  A.ola = OlaOut{};
+  if (dx) {
+    const int64_t waves = blocks * NW;
+    float* ws = reinterpret_cast<float*>(workspace);
+    A.ola.dx = dx;
+    A.ola.seams = ws + 2 * waves;
+    A.ola.margins = A.ola.seams + waves * 3 * hop;
+    A.ola.T = (int)T;
+    A.ola.Lp = (A.n_out - 1) * hop + n_fft;
+    A.ola.n_active = (int)(waves < A.total_groups ? waves : A.total_groups);
+  }
+  int r = AT_ERR_UNSUPPORTED;
+  switch (M) {
+    case 16: r = launch_mel<16>(A, (int)blocks, s); break;
+    case 32: r = launch_mel<32>(A, (int)blocks, s); break;
+    case 64: r = launch_mel<64>(A, (int)blocks, s); break;
+    case 128: r = launch_mel<128>(A, (int)blocks, s); break;
+    case 256: r = launch_mel<256>(A, (int)blocks, s); break;
+    case 512: r = launch_mel<512>(A, (int)blocks, s); break;
+    case 1024: r = launch_mel<1024>(A, (int)blocks, s); break;
+  }
+  if (r != AT_OK) return r;
+  if (dx) {
+    OlaFix F;
+    F.O = A.ola; F.rows = rows; F.total_groups = A.total_groups; F.gpr = A.gpr; F.FW = FW; F.hop = hop;
+    r = ola_fixup(F, s);
+    if (r != AT_OK) return r;
+  }
+  hipLaunchKernelGGL(mel_dist_finalize, dim3(1), dim3(256), 0, s, A.partials, (int)blocks * NW, sums);
+  AT_LAUNCH_CHECK();
+  return AT_OK;
 }
 
 }  // namespace
@@ -423,38 +515,29 @@ int at_mel_dist_f32(const float* x, const float* y, int64_t rows, int64_t T, con
   if (e != AT_OK) return e;
   if (!(clamp_eps >= FLT_MIN) || !(power > 0.f)) return AT_ERR_UNSUPPORTED;
   if (workspace_bytes < at_mel_dist_workspace_bytes(rows, T, n_fft, hop, n_mels)) return AT_ERR_INVALID;
-  const int M = n_fft / 2, FW = 64 / (M / 16);
-  MelArgs A;
-  A.x = x; A.y = y; A.window = window; A.tw = reinterpret_cast<const float2*>(twiddles);
-  A.bin_bands = bin_bands; A.bin_w = reinterpret_cast<const float2*>(bin_w); A.band_span = band_span;
-  A.G = reinterpret_cast<float2*>(G); A.partials = reinterpret_cast<float2*>(workspace);
-  A.T = (int)T; A.n_out = (int)(1 + T / hop); A.hop = hop;
-  A.gpr = (A.n_out + FW - 1) / FW;
-  A.total_groups = rows * A.gpr;
-  A.n_mels = n_mels;
-  A.eps = clamp_eps;
-  A.c_log = (float)((double)power * 0.30102999566398119521);
-  A.g_logp = (float)((double)g_log * (double)power / 2.30258509299404568402);
-  A.g_mag = g_mag;
-  A.vec2 = ((T % 2) == 0 && (reinterpret_cast<uintptr_t>(x) % 8) == 0 && (reinterpret_cast<uintptr_t>(y) % 8) == 0) ? 1 : 0;
-  int64_t blocks = mel_max_blocks(rows, T, n_fft, hop);
-  const int64_t resident = 2 * (int64_t)at::device_cu_count();      // two workgroups per CU (launch bounds; <= 72 KB of LDS each)
-  if (blocks > resident) blocks = resident;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  int r = AT_ERR_UNSUPPORTED;
-  switch (M) {
-    case 16: r = launch_mel<16>(A, (int)blocks, s); break;
-    case 32: r = launch_mel<32>(A, (int)blocks, s); break;
-    case 64: r = launch_mel<64>(A, (int)blocks, s); break;
-    case 128: r = launch_mel<128>(A, (int)blocks, s); break;
-    case 256: r = launch_mel<256>(A, (int)blocks, s); break;
-    case 512: r = launch_mel<512>(A, (int)blocks, s); break;
-    case 1024: r = launch_mel<1024>(A, (int)blocks, s); break;
-  }
-  if (r != AT_OK) return r;
-  hipLaunchKernelGGL(mel_dist_finalize, dim3(1), dim3(256), 0, s, A.partials, (int)blocks * NW, sums);
-  AT_LAUNCH_CHECK();
-  return AT_OK;
+  return mel_run(x, y, rows, T, window, twiddles, n_fft, hop, bin_bands, bin_w, band_span, n_mels, clamp_eps, power, g_log,
+                 g_mag, G, nullptr, sums, workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
+// partials (a float2 per wave), seam slots (3 hops per wave), margins (rows x n_fft)
+int64_t at_mel_dist_dx_workspace_bytes(int64_t rows, int64_t T, int n_fft, int hop, int n_mels) {
+  const int e = mel_shape_check(rows, T, n_fft, hop, n_mels);
+  if (e != AT_OK) return e;
+  const int64_t waves = dx_max_blocks(rows, T, n_fft, hop) * NW;
+  return (waves * (2 + 3 * (int64_t)hop) + rows * n_fft) * (int64_t)sizeof(float);
+}
+
+int at_mel_dist_dx_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                       int n_fft, int hop, const int* bin_bands, const float* bin_w, const int* band_span, int n_mels,
+                       float clamp_eps, float power, float g_log, float g_mag, float* dx, double* sums,
+                       void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!x || !y || !window || !twiddles || !bin_bands || !bin_w || !band_span || !dx || !sums || !workspace) return AT_ERR_INVALID;
+  const int e = mel_shape_check(rows, T, n_fft, hop, n_mels);
+  if (e != AT_OK) return e;
+  if (!(clamp_eps >= FLT_MIN) || !(power > 0.f)) return AT_ERR_UNSUPPORTED;
+  if (workspace_bytes < at_mel_dist_dx_workspace_bytes(rows, T, n_fft, hop, n_mels)) return AT_ERR_INVALID;
+  return mel_run(x, y, rows, T, window, twiddles, n_fft, hop, bin_bands, bin_w, band_span, n_mels, clamp_eps, power, g_log,
+                 g_mag, nullptr, dx, sums, workspace, reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

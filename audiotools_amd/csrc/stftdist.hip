@@ -18,9 +18,12 @@
 //  * G leaves through the slab as 512-byte non-temporal runs (bin-contiguous (rows, N, F)); without G there is no large store;
 //  * two float accumulators per lane over the whole run, one wave reduction, one partial pair per wave in the workspace;
 //    a one-workgroup kernel adds the partials in double in a fixed order: no atomics, bit-equal sums on every run;
-//  * frame slots past a row's last frame repeat that frame (as in stft.hip) but add nothing and store nothing.
+//  * frame slots past a row's last frame repeat that frame (as in stft.hip) but add nothing and store nothing;
+//  * MODE: DIST_NONE (sums), DIST_G (sums and G, above), DIST_DX (sums and the gradient of the SIGNAL: G stays in the slab and
+//    goes through the adjoint transform and the in-wave overlap-add of dist_ola.h; at_stft_dist_dx_f32).
 #include "at_common.h"
 #include "fft_wave.h"
+#include "dist_ola.h"
 #include <float.h>
 
 extern "C" int at_stft_fused_supported(int n_fft);
@@ -47,16 +50,21 @@ struct DistArgs {
   float g_logp;            // g_log * power / ln 10
   float g_mag;
   int vec2;                // rows of x and y are 8-byte aligned: float2 loads
+  OlaOut ola;              // DIST_DX only: where the waveform gradient goes (dist_ola.h)
 };
 
+// DIST_DX adds the carries of the overlap-add: 24 L floats per wave
 template <int M>
-constexpr int lds_floats() { return NW * 2 * WAVE_LDS_SLOTS + 2 * M + M + 16 * 36; }
+constexpr int lds_floats(int mode = DIST_NONE) {
+  return NW * 2 * WAVE_LDS_SLOTS + 2 * M + M + 16 * 36 + (mode == DIST_DX ? NW * ola_carry_floats<M>() : 0);
+}
 
 __device__ __forceinline__ float abs2(float2 z) { return fmaf(z.x, z.x, z.y * z.y); }
 __device__ __forceinline__ float sgnf(float a, float b) { return (a > b ? 1.f : 0.f) - (a < b ? 1.f : 0.f); }
 
-template <int M, bool GRAD>
+template <int M, int MODE>
 __global__ __launch_bounds__(NW * 64, 2) void stft_dist_kernel(const DistArgs A) {
+  constexpr bool GRAD = MODE != DIST_NONE;
   using P = Plan<M>;
   constexpr int L = P::L, FW = P::FW, N = 2 * M;
   // LDS (floats): [NW wave slabs][window, halved: 2M][split twiddles: M][pass-2 twiddles: 16 rows x 36]
@@ -81,6 +89,10 @@ __global__ __launch_bounds__(NW * 64, 2) void stft_dist_kernel(const DistArgs A)
   const int t = lane % L;   // thread inside the frame
   float2* wbuf = reinterpret_cast<float2*>(lds_f) + wave * WAVE_LDS_SLOTS;
   float2* fbuf = wbuf + fs * P::SLOTS;
+  float* carry = s_tw2 + 16 * 36 + wave * ola_carry_floats<M>();   // DIST_DX only: lane-private, element i is lane i % 64's
+  if constexpr (MODE == DIST_DX) {
+    for (int i = lane; i < ola_carry_floats<M>(); i += 64) carry[i] = 0.f;
+  }
 
   constexpr int NB2 = 16 / P::R2;
   constexpr int NB3 = 16 / P::R3;
@@ -186,10 +198,14 @@ __global__ __launch_bounds__(NW * 64, 2) void stft_dist_kernel(const DistArgs A)
   };
 
   // ---- this wave's run of frame groups
-  const int64_t n_waves = (int64_t)gridDim.x * NW;
+  // (DIST_DX: only the first n_active <= total_groups waves own groups, so that no run is empty)
+  const int64_t n_waves = MODE == DIST_DX ? (int64_t)A.ola.n_active : (int64_t)gridDim.x * NW;
   const int64_t gw = (int64_t)blockIdx.x * NW + wave;
-  const int64_t g_lo = A.total_groups * gw / n_waves;
-  const int64_t g_hi = A.total_groups * (gw + 1) / n_waves;
+  int64_t g_lo = A.total_groups * gw / n_waves;
+  int64_t g_hi = A.total_groups * (gw + 1) / n_waves;
+  if constexpr (MODE == DIST_DX) {
+    if (gw >= n_waves) g_lo = g_hi = 0;
+  }
   float s_log = 0.f, s_mag = 0.f;
 
   for (int64_t g = g_lo; g < g_hi; ++g) {
@@ -252,6 +268,13 @@ __global__ __launch_bounds__(NW * 64, 2) void stft_dist_kernel(const DistArgs A)
       if constexpr (GRAD) {
         if (t == 0) sx[M / 2] = gh;
         wave_sync();
+      }
+      if constexpr (MODE == DIST_DX) {
+        // G stays on chip: adjoint transform of every frame, overlap-add inside the wave (dist_ola.h)
+        ola_frame<M>(fbuf, wbuf, s_win, s_twp, s_tw2, tw3b, t, fs, valid);
+        ola_group<M>(reinterpret_cast<const float*>(wbuf), carry, lane, A.ola, row, f0, gb == A.gpr - 1);
+      }
+      if constexpr (MODE == DIST_G) {
         // the FW frames of the group are consecutive rows of G: (M + 1) FW contiguous float2, streamed as 512-byte runs
         constexpr int TOT = FW * (M + 1);
         constexpr int NST = (TOT + 63) / 64;
@@ -267,6 +290,11 @@ __global__ __launch_bounds__(NW * 64, 2) void stft_dist_kernel(const DistArgs A)
         }
         wave_sync();
       }
+    }
+  }
+  if constexpr (MODE == DIST_DX) {
+    if (g_hi > g_lo && g_hi % A.gpr != 0) {     // the run ends inside a row: its carry is the next wave's missing part
+      for (int i = lane; i < ola_carry_floats<M>(); i += 64) A.ola.seams[gw * ola_carry_floats<M>() + i] = carry[i];
     }
   }
   s_log = at::wave_sum(s_log);
@@ -300,13 +328,23 @@ __global__ __launch_bounds__(256) void stft_dist_finalize(const float2* __restri
   }
 }
 
-template <int M>
-int launch_dist(const DistArgs& A, int blocks, hipStream_t stream) {
-  const size_t bytes = (size_t)lds_floats<M>() * 4;   // <= 49408 B: no raised LDS limit needed
-  if (A.G) hipLaunchKernelGGL((stft_dist_kernel<M, true>), dim3((unsigned)blocks), dim3(NW * 64), bytes, stream, A);
-  else hipLaunchKernelGGL((stft_dist_kernel<M, false>), dim3((unsigned)blocks), dim3(NW * 64), bytes, stream, A);
+template <int M, int MODE>
+int launch_mode(const DistArgs& A, int blocks, hipStream_t stream) {
+  auto kern = stft_dist_kernel<M, MODE>;
+  const size_t bytes = (size_t)lds_floats<M>(MODE) * 4;   // <= 49408 B; DIST_DX at n_fft 2048: 73984 B, still two workgroups per CU
+  if (bytes > 64 * 1024) {
+    const int e = at::allow_big_lds(reinterpret_cast<const void*>(kern));
+    if (e != AT_OK) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NW * 64), bytes, stream, A);
   AT_LAUNCH_CHECK();
   return AT_OK;
+}
+
+template <int M>
+int launch_dist(const DistArgs& A, int blocks, hipStream_t stream) {
+  if (A.ola.dx) return launch_mode<M, DIST_DX>(A, blocks, stream);
+  return A.G ? launch_mode<M, DIST_G>(A, blocks, stream) : launch_mode<M, DIST_NONE>(A, blocks, stream);
 }
 
 // AT_OK when the kernel takes the shape
@@ -323,6 +361,65 @@ int64_t dist_max_blocks(int64_t rows, int64_t T, int n_fft, int hop) {
   const int64_t gpr = (1 + T / hop + FW - 1) / FW;
   const int64_t blocks = (rows * gpr + NW - 1) / NW;
   return blocks < MAX_BLOCKS ? blocks : MAX_BLOCKS;
+}
+
+// persistent grid of the waveform mode: never more than the resident workgroups, so that the seam slots stay small
+int64_t dx_max_blocks(int64_t rows, int64_t T, int n_fft, int hop) {
+  const int64_t blocks = dist_max_blocks(rows, T, n_fft, hop);
+  const int64_t resident = 2 * (int64_t)at::device_cu_count();
+  return blocks < resident ? blocks : resident;
+}
+
+// G != null: dL/dX; dx != null: dL/dx through the overlap-add tail (workspace: partials, seam slots, margins)
+int dist_run(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles, int n_fft,
+             int hop, float clamp_eps, float power, float g_log, float g_mag, float* G, float* dx, double* sums,
+             void* workspace, hipStream_t s) {
+  const int M = n_fft / 2, FW = 64 / (M / 16);
+  DistArgs A;
+  A.x = x; A.y = y; A.window = window; A.tw = reinterpret_cast<const float2*>(twiddles);
+  A.G = reinterpret_cast<float2*>(G); A.partials = reinterpret_cast<float2*>(workspace);
+  A.T = (int)T; A.n_out = (int)(1 + T / hop); A.hop = hop;
+  A.gpr = (A.n_out + FW - 1) / FW;
+  A.total_groups = rows * A.gpr;
+  A.eps = clamp_eps; A.eps2 = clamp_eps * clamp_eps;
+  A.c_log = (float)(0.5 * (double)power * 0.30102999566398119521);
+  A.g_logp = (float)((double)g_log * (double)power / 2.30258509299404568402);
+  A.g_mag = g_mag;
+  A.vec2 = ((T % 2) == 0 && (reinterpret_cast<uintptr_t>(x) % 8) == 0 && (reinterpret_cast<uintptr_t>(y) % 8) == 0) ? 1 : 0;
+  int64_t blocks = dist_max_blocks(rows, T, n_fft, hop);
+  const int64_t resident = 2 * (int64_t)at::device_cu_count();      // two workgroups per CU (launch bounds; 49 KB / 74 KB of LDS each)
+  if (blocks > resident) blocks = resident;
+  A.ola = OlaOut{};
+  if (dx) {
+    const int64_t waves = blocks * NW;
+    float* ws = reinterpret_cast<float*>(workspace);
+    A.ola.dx = dx;
+    A.ola.seams = ws + 2 * waves;
+    A.ola.margins = A.ola.seams + waves * 3 * hop;
+    A.ola.T = (int)T;
+    A.ola.Lp = (A.n_out - 1) * hop + n_fft;
+    A.ola.n_active = (int)(waves < A.total_groups ? waves : A.total_groups);
+  }
+  int r = AT_ERR_UNSUPPORTED;
+  switch (M) {
+    case 16: r = launch_dist<16>(A, (int)blocks, s); break;
+    case 32: r = launch_dist<32>(A, (int)blocks, s); break;
+    case 64: r = launch_dist<64>(A, (int)blocks, s); break;
+    case 128: r = launch_dist<128>(A, (int)blocks, s); break;
+    case 256: r = launch_dist<256>(A, (int)blocks, s); break;
+    case 512: r = launch_dist<512>(A, (int)blocks, s); break;
+    case 1024: r = launch_dist<1024>(A, (int)blocks, s); break;
+  }
+  if (r != AT_OK) return r;
+  if (dx) {
+    OlaFix F;
+    F.O = A.ola; F.rows = rows; F.total_groups = A.total_groups; F.gpr = A.gpr; F.FW = FW; F.hop = hop;
+    r = ola_fixup(F, s);
+    if (r != AT_OK) return r;
+  }
+  hipLaunchKernelGGL(stft_dist_finalize, dim3(1), dim3(256), 0, s, A.partials, (int)blocks * NW, sums);
+  AT_LAUNCH_CHECK();
+  return AT_OK;
 }
 
 }  // namespace
@@ -343,36 +440,28 @@ int at_stft_dist_f32(const float* x, const float* y, int64_t rows, int64_t T, co
   if (e != AT_OK) return e;
   if (!(clamp_eps * clamp_eps >= FLT_MIN) || !(power > 0.f)) return AT_ERR_UNSUPPORTED;
   if (workspace_bytes < at_stft_dist_workspace_bytes(rows, T, n_fft, hop)) return AT_ERR_INVALID;
-  const int M = n_fft / 2, FW = 64 / (M / 16);
-  DistArgs A;
-  A.x = x; A.y = y; A.window = window; A.tw = reinterpret_cast<const float2*>(twiddles);
-  A.G = reinterpret_cast<float2*>(G); A.partials = reinterpret_cast<float2*>(workspace);
-  A.T = (int)T; A.n_out = (int)(1 + T / hop); A.hop = hop;
-  A.gpr = (A.n_out + FW - 1) / FW;
-  A.total_groups = rows * A.gpr;
-  A.eps = clamp_eps; A.eps2 = clamp_eps * clamp_eps;
-  A.c_log = (float)(0.5 * (double)power * 0.30102999566398119521);
-  A.g_logp = (float)((double)g_log * (double)power / 2.30258509299404568402);
-  A.g_mag = g_mag;
-  A.vec2 = ((T % 2) == 0 && (reinterpret_cast<uintptr_t>(x) % 8) == 0 && (reinterpret_cast<uintptr_t>(y) % 8) == 0) ? 1 : 0;
-  int64_t blocks = dist_max_blocks(rows, T, n_fft, hop);
-  const int64_t resident = 2 * (int64_t)at::device_cu_count();      // two workgroups per CU (launch bounds; 49 KB of LDS each)
-  if (blocks > resident) blocks = resident;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  int r = AT_ERR_UNSUPPORTED;
-  switch (M) {
-    case 16: r = launch_dist<16>(A, (int)blocks, s); break;
-    case 32: r = launch_dist<32>(A, (int)blocks, s); break;
-    case 64: r = launch_dist<64>(A, (int)blocks, s); break;
-    case 128: r = launch_dist<128>(A, (int)blocks, s); break;
-    case 256: r = launch_dist<256>(A, (int)blocks, s); break;
-    case 512: r = launch_dist<512>(A, (int)blocks, s); break;
-    case 1024: r = launch_dist<1024>(A, (int)blocks, s); break;
-  }
-  if (r != AT_OK) return r;
-  hipLaunchKernelGGL(stft_dist_finalize, dim3(1), dim3(256), 0, s, A.partials, (int)blocks * NW, sums);
-  AT_LAUNCH_CHECK();
-  return AT_OK;
+  return dist_run(x, y, rows, T, window, twiddles, n_fft, hop, clamp_eps, power, g_log, g_mag, G, nullptr, sums, workspace,
+                  reinterpret_cast<hipStream_t>(stream));
+}
+
+// partials (a float2 per wave), seam slots (3 hops per wave), margins (rows x n_fft)
+int64_t at_stft_dist_dx_workspace_bytes(int64_t rows, int64_t T, int n_fft, int hop) {
+  const int e = dist_shape_check(rows, T, n_fft, hop);
+  if (e != AT_OK) return e;
+  const int64_t waves = dx_max_blocks(rows, T, n_fft, hop) * NW;
+  return (waves * (2 + 3 * (int64_t)hop) + rows * n_fft) * (int64_t)sizeof(float);
+}
+
+int at_stft_dist_dx_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                        int n_fft, int hop, float clamp_eps, float power, float g_log, float g_mag, float* dx, double* sums,
+                        void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!x || !y || !window || !twiddles || !dx || !sums || !workspace) return AT_ERR_INVALID;
+  const int e = dist_shape_check(rows, T, n_fft, hop);
+  if (e != AT_OK) return e;
+  if (!(clamp_eps * clamp_eps >= FLT_MIN) || !(power > 0.f)) return AT_ERR_UNSUPPORTED;
+  if (workspace_bytes < at_stft_dist_dx_workspace_bytes(rows, T, n_fft, hop)) return AT_ERR_INVALID;
+  return dist_run(x, y, rows, T, window, twiddles, n_fft, hop, clamp_eps, power, g_log, g_mag, nullptr, dx, sums, workspace,
+                  reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -691,6 +691,72 @@ def mel_distance(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_fft: 
     return sums, (None if G is None else G.transpose(2, 3))
 
 
+def stft_distance_dx_supported(n_fft: int, hop: int, T: int, clamp_eps: float, power: float) -> bool:
+    """The waveform mode of the fused distance kernel takes every scale :func:`stft_distance_supported` takes."""
+    return stft_distance_supported(n_fft, hop, T, clamp_eps, power)
+
+
+def stft_distance_dx(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_fft: int, hop: int, clamp_eps: float,
+                     power: float, g_log: float, g_mag: float):
+    """:func:`stft_distance` with the gradient taken all the way to the signal inside the kernel (csrc/dist_ola.h).
+
+    Returns ``(sums, dx)``: ``sums`` as there, ``dx`` = ``g_log`` d sums[0]/dx + ``g_mag`` d sums[1]/dx, float32 (B, C, T).
+    No spectrum-shaped tensor exists at any time; ``dx`` is the only large allocation."""
+    _require_native_ok(x)
+    _require_native_ok(y)
+    if x.shape != y.shape or x.ndim != 3 or x.dtype != torch.float32 or y.dtype != torch.float32 or x.device != y.device:
+        raise ValueError("stft_distance_dx: two float32 (B, C, T) tensors of one shape on one device")
+    B, C, T = x.shape
+    x, y = x.contiguous(), y.contiguous()
+    dev = x.device
+    lib = _native.lib()
+    nbytes = lib.at_stft_dist_dx_workspace_bytes(B * C, T, n_fft, hop)
+    _native.check(min(nbytes, 0), "at_stft_dist_dx_workspace_bytes")
+    ws = _workspace(nbytes, dev)
+    sums = torch.empty(2, dtype=torch.float64, device=dev)
+    dx = _alloc_retry(lambda: torch.empty((B, C, T), dtype=torch.float32, device=dev))
+    code = lib.at_stft_dist_dx_f32(_native.ptr(x), _native.ptr(y), B * C, T, _native.ptr(window),
+                                   _native.ptr(tables.stft_twiddles(n_fft, dev)), n_fft, hop, clamp_eps, power, g_log, g_mag,
+                                   _native.ptr(dx), _native.ptr(sums), _native.ptr(ws), ws.numel(), _native.current_stream(dev))
+    _native.check(code, "at_stft_dist_dx_f32")
+    return sums, dx
+
+
+def mel_distance_dx_supported(n_fft: int, hop: int, T: int, n_mels: int, clamp_eps: float, power: float) -> bool:
+    """The waveform mode of the fused mel distance kernel takes every scale :func:`mel_distance_supported` takes (all seven
+    sizes build without scratch; n_fft 2048 runs one workgroup per CU)."""
+    return mel_distance_supported(n_fft, hop, T, n_mels, clamp_eps, power)
+
+
+def mel_distance_dx(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_fft: int, hop: int, mel_tables, n_mels: int,
+                    clamp_eps: float, power: float, g_log: float, g_mag: float):
+    """:func:`mel_distance` with the gradient taken all the way to the signal inside the kernel (csrc/dist_ola.h).
+
+    Returns ``(sums, dx)``: ``sums`` as there, ``dx`` = ``g_log`` d sums[0]/dx + ``g_mag`` d sums[1]/dx, float32 (B, C, T)."""
+    _require_native_ok(x)
+    _require_native_ok(y)
+    if x.shape != y.shape or x.ndim != 3 or x.dtype != torch.float32 or y.dtype != torch.float32 or x.device != y.device:
+        raise ValueError("mel_distance_dx: two float32 (B, C, T) tensors of one shape on one device")
+    B, C, T = x.shape
+    x, y = x.contiguous(), y.contiguous()
+    dev = x.device
+    bands, w, spans = mel_tables
+    if bands.numel() != n_fft // 2 + 1 or w.numel() != 2 * bands.numel() or spans.numel() != n_mels:
+        raise ValueError("mel_distance_dx: tables of another filterbank")
+    lib = _native.lib()
+    nbytes = lib.at_mel_dist_dx_workspace_bytes(B * C, T, n_fft, hop, n_mels)
+    _native.check(min(nbytes, 0), "at_mel_dist_dx_workspace_bytes")
+    ws = _workspace(nbytes, dev)
+    sums = torch.empty(2, dtype=torch.float64, device=dev)
+    dx = _alloc_retry(lambda: torch.empty((B, C, T), dtype=torch.float32, device=dev))
+    code = lib.at_mel_dist_dx_f32(_native.ptr(x), _native.ptr(y), B * C, T, _native.ptr(window),
+                                  _native.ptr(tables.stft_twiddles(n_fft, dev)), n_fft, hop, _native.ptr(bands), _native.ptr(w),
+                                  _native.ptr(spans), n_mels, clamp_eps, power, g_log, g_mag, _native.ptr(dx), _native.ptr(sums),
+                                  _native.ptr(ws), ws.numel(), _native.current_stream(dev))
+    _native.check(code, "at_mel_dist_dx_f32")
+    return sums, dx
+
+
 def istft_adjoint_supported(n_fft: int, hop: int) -> bool:
     return istft_fused_supported(n_fft, hop) and (n_fft // 2) % hop == 0 and stft_fused_supported(n_fft)
 

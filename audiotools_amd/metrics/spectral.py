@@ -5,7 +5,8 @@ require gradients those run the fused forward kernels and their adjoints
 (``spectral._NativeStft`` / ``_NativeStftMel``), so a multi-scale mel loss never materialises a
 spectrum gradient in HBM.  ``MultiScaleSTFTLoss(fused=True)`` goes further: one kernel per scale takes both signals
 to the loss sums and dL/dX (``csrc/stftdist.hip``), no spectrum is written at all; ``MelSpectrogramLoss(fused=True)`` is
-the same for the mel distance (``csrc/meldist.hip``)."""
+the same for the mel distance (``csrc/meldist.hip``).  ``fused="waveform"`` also keeps dL/dX on chip: the kernel returns the
+loss sums and the gradient of the SIGNAL (``csrc/dist_ola.h``), backward is one multiplication."""
 import typing
 
 import numpy as np
@@ -51,6 +52,27 @@ class _StftDistance(torch.autograd.Function):
         return (kernels.stft_adjoint(G, window, n_fft, hop, T) * grad_out,) + (None,) * 8
 
 
+class _StftDistanceWave(torch.autograd.Function):
+    """:class:`_StftDistance` with the gradient of the signal formed inside the kernel (``kernels.stft_distance_dx``):
+    no dL/dX in memory, no adjoint launch, no clone and no fold in backward."""
+
+    @staticmethod
+    def forward(ctx, est, ref, window, n_fft, hop, clamp_eps, power, log_weight, mag_weight):
+        B, C, T = est.shape
+        count = B * C * (1 + T // hop) * (n_fft // 2 + 1)
+        args = (est.detach(), ref.detach(), window, n_fft, hop, clamp_eps, power, log_weight / count, mag_weight / count)
+        if ctx.needs_input_grad[0]:
+            sums, dx = kernels.stft_distance_dx(*args)
+            ctx.save_for_backward(dx)
+        else:
+            sums, _ = kernels.stft_distance(*args, False)
+        return (sums[0] * (log_weight / count) + sums[1] * (mag_weight / count)).to(est.dtype)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return (ctx.saved_tensors[0] * grad_out,) + (None,) * 8
+
+
 class MultiScaleSTFTLoss(nn.Module):
     """Multi-resolution STFT magnitude distance (DDSP, Engel et al. 2019; spectral.py:11-94):
     for every window length w (hop w/4) the log-power and the linear magnitudes are compared with
@@ -59,7 +81,8 @@ class MultiScaleSTFTLoss(nn.Module):
     ``fused=True`` (not in the reference) evaluates every scale that qualifies with the fused distance kernel: both
     signals float32 HIP tensors of one shape, ``loss_fn`` an ``nn.L1Loss`` with mean reduction, at most one signal requiring
     a gradient, a power-of-two window of 32 ... 2048.  Such a scale does NOT touch ``stft_data`` of either signal; every
-    other scale runs the code of ``fused=False``."""
+    other scale runs the code of ``fused=False``.  ``fused="waveform"``: the same scales, with the gradient of the signal
+    from the kernel itself (no spectrum gradient in memory, no adjoint launch)."""
 
     def __init__(self, window_lengths: typing.List[int] = [2048, 512], loss_fn: typing.Callable = nn.L1Loss(),
                  clamp_eps: float = 1e-5, mag_weight: float = 1.0, log_weight: float = 1.0, pow: float = 2.0,
@@ -82,12 +105,14 @@ class MultiScaleSTFTLoss(nn.Module):
         wtype = s.window_type or x.stft_params.window_type
         if (gx and gy) or wtype != (s.window_type or y.stft_params.window_type):
             return None
-        if not kernels.stft_distance_supported(s.window_length, s.hop_length, xa.shape[-1], self.clamp_eps, self.pow):
+        supported = kernels.stft_distance_dx_supported if self.fused == "waveform" else kernels.stft_distance_supported
+        if not supported(s.window_length, s.hop_length, xa.shape[-1], self.clamp_eps, self.pow):
             return None
         est, ref = (ya, xa) if gy else (xa, ya)          # L1 is symmetric: the signal that needs a gradient is the estimate
         window = x.get_window(wtype, s.window_length, str(xa.device))
-        return _StftDistance.apply(est, ref, window, s.window_length, s.hop_length, float(self.clamp_eps), float(self.pow),
-                                   float(self.log_weight), float(self.mag_weight))
+        fn = _StftDistanceWave if self.fused == "waveform" else _StftDistance
+        return fn.apply(est, ref, window, s.window_length, s.hop_length, float(self.clamp_eps), float(self.pow),
+                        float(self.log_weight), float(self.mag_weight))
 
     def forward(self, x, y):
         total = 0.0
@@ -126,6 +151,27 @@ class _MelDistance(torch.autograd.Function):
         return (kernels.stft_adjoint(G, window, n_fft, hop, T) * grad_out,) + (None,) * 10
 
 
+class _MelDistanceWave(torch.autograd.Function):
+    """:class:`_MelDistance` with the gradient of the signal formed inside the kernel (``kernels.mel_distance_dx``)."""
+
+    @staticmethod
+    def forward(ctx, est, ref, window, n_fft, hop, mel_tables, n_mels, clamp_eps, power, log_weight, mag_weight):
+        B, C, T = est.shape
+        count = B * C * (1 + T // hop) * n_mels
+        args = (est.detach(), ref.detach(), window, n_fft, hop, mel_tables, n_mels, clamp_eps, power, log_weight / count,
+                mag_weight / count)
+        if ctx.needs_input_grad[0]:
+            sums, dx = kernels.mel_distance_dx(*args)
+            ctx.save_for_backward(dx)
+        else:
+            sums, _ = kernels.mel_distance(*args, False)
+        return (sums[0] * (log_weight / count) + sums[1] * (mag_weight / count)).to(est.dtype)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return (ctx.saved_tensors[0] * grad_out,) + (None,) * 10
+
+
 class MelSpectrogramLoss(nn.Module):
     """Multi-resolution mel-spectrogram distance (spectral.py:97-194): scale i uses
     ``n_mels[i]`` bands between ``mel_fmin[i]`` and ``mel_fmax[i]`` on a window of
@@ -134,7 +180,8 @@ class MelSpectrogramLoss(nn.Module):
     ``fused=True`` (not in the reference) evaluates every scale that qualifies with the fused mel distance kernel: both
     signals float32 HIP tensors of one shape and sample rate, ``loss_fn`` an ``nn.L1Loss`` with mean reduction, at most one
     signal requiring a gradient, a power-of-two window of 32 ... 2048 and at most window / 4 bands.  Such a scale does NOT
-    touch ``stft_data`` of either signal; every other scale runs the code of ``fused=False``."""
+    touch ``stft_data`` of either signal; every other scale runs the code of ``fused=False``.  ``fused="waveform"``: the same
+    scales, with the gradient of the signal from the kernel itself."""
 
     def __init__(self, n_mels: typing.List[int] = [150, 80], window_lengths: typing.List[int] = [2048, 512],
                  loss_fn: typing.Callable = nn.L1Loss(), clamp_eps: float = 1e-5, mag_weight: float = 1.0,
@@ -160,15 +207,17 @@ class MelSpectrogramLoss(nn.Module):
         wtype = s.window_type or x.stft_params.window_type
         if (gx and gy) or wtype != (s.window_type or y.stft_params.window_type):
             return None
-        if not kernels.mel_distance_supported(s.window_length, s.hop_length, xa.shape[-1], n_mels, self.clamp_eps, self.pow):
+        supported = kernels.mel_distance_dx_supported if self.fused == "waveform" else kernels.mel_distance_supported
+        if not supported(s.window_length, s.hop_length, xa.shape[-1], n_mels, self.clamp_eps, self.pow):
             return None
         mel_tables = tables.mel_dist_tables(x.sample_rate, s.window_length, n_mels, fmin, fmax, xa.device)
         if mel_tables is None:
             return None
         est, ref = (ya, xa) if gy else (xa, ya)          # L1 is symmetric: the signal that needs a gradient is the estimate
         window = x.get_window(wtype, s.window_length, str(xa.device))
-        return _MelDistance.apply(est, ref, window, s.window_length, s.hop_length, mel_tables, n_mels, float(self.clamp_eps),
-                                  float(self.pow), float(self.log_weight), float(self.mag_weight))
+        fn = _MelDistanceWave if self.fused == "waveform" else _MelDistance
+        return fn.apply(est, ref, window, s.window_length, s.hop_length, mel_tables, n_mels, float(self.clamp_eps),
+                        float(self.pow), float(self.log_weight), float(self.mag_weight))
 
     def forward(self, x, y):
         total = 0.0

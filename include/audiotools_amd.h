@@ -195,6 +195,25 @@ int at_mel_dist_f32(const float* x, const float* y, int64_t rows, int64_t T, con
                     float clamp_eps, float power, float g_log, float g_mag, float* G, double* sums,
                     void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- fused distances, waveform mode: loss sums and dL/dx of one scale, no spectrum-shaped tensor ----------
+ * The arguments, checks and return codes of at_stft_dist_f32 / at_mel_dist_f32 with  dx (rows, T) f32  in place of G (NULL dx:
+ * AT_ERR_INVALID): the kernel forms G on chip, applies the adjoint of the windowed one-sided DFT per frame (conventions of
+ * at_stft_adjoint_f32: no 1/N, no factor 2 on interior bins), overlap-adds inside the wave and folds the two reflected
+ * margins of the centre padding, so that  dx = g_log d sums[0]/dx + g_mag d sums[1]/dx.  No atomics: sums and dx are
+ * bit-equal for equal inputs on one device.
+ *   workspace at_*_dist_dx_workspace_bytes(...) bytes: a partial pair and a seam slot of 3 hops per wave of the persistent
+ *             grid, and rows x n_fft margin floats (a negative error for shapes the kernel does not take)
+ */
+int64_t at_stft_dist_dx_workspace_bytes(int64_t rows, int64_t T, int n_fft, int hop);
+int at_stft_dist_dx_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                        int n_fft, int hop, float clamp_eps, float power, float g_log, float g_mag, float* dx, double* sums,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+int64_t at_mel_dist_dx_workspace_bytes(int64_t rows, int64_t T, int n_fft, int hop, int n_mels);
+int at_mel_dist_dx_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                       int n_fft, int hop, const int* bin_bands, const float* bin_w, const int* band_span, int n_mels,
+                       float clamp_eps, float power, float g_log, float g_mag, float* dx, double* sums,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- BS.1770 integrated loudness ---------------------------------------------------
  * Replaces  audiotools/core/loudness.py:102-126  (2x torchaudio.functional.lfilter, the
  *           CPU/IIR branch), :164-174 (julius.core.unfold), :176-247 (gated integration).

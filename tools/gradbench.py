@@ -84,24 +84,27 @@ if CASE in ("all", "dacmel"):
     print("7-scale grad rel diff", float((d1 - d2).abs().max() / d2.abs().max()))
 
 
+MODES = (False, True, "waveform")    # unfused, fused with G + native adjoint, fused with the waveform gradient in-kernel
+
+
 def run_dac_mel_fused(rounds=5, reps=10):
-    """The same 7-scale loss, forward + backward: fused=True (csrc/meldist.hip) against fused=False, alternating in one
-    process, every window timed with HIP events; then the kernel alone per scale, with and without G."""
+    """The same 7-scale loss, forward + backward: fused=True (csrc/meldist.hip) and fused="waveform" against fused=False, alternating in one
+    process, every window timed with HIP events; then the kernel alone per scale: with G, without, with dx (waveform mode)."""
     from audiotools_amd import kernels, metrics, tables
     mels, wins = [5, 10, 20, 40, 80, 160, 320], [32, 64, 128, 256, 512, 1024, 2048]
     xs, ys = x[:32], (x[32:64] if B >= 64 else x[:32].flip(0)).clone()
     losses = {f: metrics.spectral.MelSpectrogramLoss(n_mels=mels, window_lengths=wins, mel_fmin=[0] * 7, mel_fmax=[None] * 7,
-                                                     pow=1.0, mag_weight=0.0, fused=f) for f in (False, True)}
+                                                     pow=1.0, mag_weight=0.0, fused=f) for f in MODES}
 
     def fn(fused):
         xa = xs.clone().requires_grad_(True)
         losses[fused](A.AudioSignal(xa, 44100), A.AudioSignal(ys, 44100)).backward()
         return xa.grad
 
-    grads = {f: fn(f) for f in (False, True)}          # warm-up of both paths (code objects, allocator, tables)
-    times = {False: [], True: []}
+    grads = {f: fn(f) for f in MODES}          # warm-up of both paths (code objects, allocator, tables)
+    times = {f: [] for f in MODES}
     for _ in range(rounds):
-        for f in (False, True):
+        for f in MODES:
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record()
             for _ in range(reps):
@@ -109,27 +112,33 @@ def run_dac_mel_fused(rounds=5, reps=10):
             t1.record()
             t1.synchronize()
             times[f].append(t0.elapsed_time(t1) / reps)
-    for f in (False, True):
+    for f in MODES:
         ts = sorted(times[f])
         print(f"7-scale MelSpectrogramLoss fwd + bwd, 32x2chx10s, fused={f}: median {ts[len(ts) // 2]:8.2f} ms  "
               f"(min {ts[0]:.2f}, max {ts[-1]:.2f}; {rounds} windows of {reps})", flush=True)
-    print("fused vs unfused grad rel diff", float((grads[True] - grads[False]).abs().max() / grads[False].abs().max()))
+    for f in MODES[1:]:
+        print(f"fused={f} vs unfused grad rel diff", float((grads[f] - grads[False]).abs().max() / grads[False].abs().max()))
     S = xs.numel() * 4
     for n_mels, n_fft in zip(mels, wins):
         win = A.AudioSignal.get_window("hann", n_fft, str(xs.device))
         tb = tables.mel_dist_tables(44100, n_fft, n_mels, 0, None, xs.device)
-        for want in (True, False):
+        for want in (True, False, "dx", "G+adjoint"):
             call = lambda: kernels.mel_distance(xs, ys, win, n_fft, n_fft // 4, tb, n_mels, 1e-5, 1.0, 1e-9, 0.0, want)
+            if want == "dx":
+                call = lambda: kernels.mel_distance_dx(xs, ys, win, n_fft, n_fft // 4, tb, n_mels, 1e-5, 1.0, 1e-9, 0.0)
+            if want == "G+adjoint":     # what the waveform mode replaces: the G kernel, at_stft_adjoint_f32, the clone and the folds
+                call = lambda: kernels.stft_adjoint(kernels.mel_distance(xs, ys, win, n_fft, n_fft // 4, tb, n_mels, 1e-5, 1.0, 1e-9, 0.0, True)[1],
+                                                    win, n_fft, n_fft // 4, xs.shape[-1])
             call()
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record()
-            for _ in range(10):
+            for _ in range(50):
                 call()
             t1.record()
             t1.synchronize()
-            ms = t0.elapsed_time(t1) / 10
-            nbytes = 2 * S + (4 * S if want else 0)
-            print(f"at_mel_dist_f32 n_fft={n_fft} n_mels={n_mels} G={want}: {ms:7.3f} ms, {nbytes / ms / 1e6:.0f} GB/s of its {nbytes / 1e9:.2f} GB", flush=True)
+            ms = t0.elapsed_time(t1) / 50
+            nbytes = 2 * S + {True: 4 * S, False: 0, "dx": S}.get(want, 12 * S)     # G+adjoint: 4 S out, 4 S in, ~4 S of OLA, clone, folds
+            print(f"at_mel_dist_f32 n_fft={n_fft} n_mels={n_mels} out={ {True: 'G', False: 'none'}.get(want, want) }: {ms:7.3f} ms, {nbytes / ms / 1e6:.0f} GB/s of its {nbytes / 1e9:.2f} GB", flush=True)
 
 
 if CASE in ("all", "dacmel"):
@@ -138,20 +147,21 @@ if CASE in ("all", "dacmel"):
 
 def run_msstft(rounds=5, reps=20):
     """MultiScaleSTFTLoss at its default scales (2048, 512), estimate vs target of 32 x 2 ch x 10 s each, forward + backward:
-    fused=True (csrc/stftdist.hip) against fused=False, alternating in one process, every window timed with HIP events."""
+    fused=True (csrc/stftdist.hip) and fused="waveform" (csrc/dist_ola.h) against fused=False, alternating in one process, every
+    window timed with HIP events."""
     from audiotools_amd import metrics
     xs, ys = x[:32], (x[32:64] if B >= 64 else x[:32].flip(0)).clone()
-    losses = {f: metrics.spectral.MultiScaleSTFTLoss(fused=f) for f in (False, True)}
+    losses = {f: metrics.spectral.MultiScaleSTFTLoss(fused=f) for f in MODES}
 
     def fn(fused):
         xa = xs.clone().requires_grad_(True)
         losses[fused](A.AudioSignal(xa, 44100), A.AudioSignal(ys, 44100)).backward()
         return xa.grad
 
-    grads = {f: fn(f) for f in (False, True)}          # warm-up of both paths (code objects, allocator, tables)
-    times = {False: [], True: []}
+    grads = {f: fn(f) for f in MODES}          # warm-up of both paths (code objects, allocator, tables)
+    times = {f: [] for f in MODES}
     for _ in range(rounds):
-        for f in (False, True):
+        for f in MODES:
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record()
             for _ in range(reps):
@@ -159,7 +169,7 @@ def run_msstft(rounds=5, reps=20):
             t1.record()
             t1.synchronize()
             times[f].append(t0.elapsed_time(t1) / reps)
-    for f in (False, True):
+    for f in MODES:
         ts = sorted(times[f])
         print(f"MultiScaleSTFTLoss [2048, 512] fwd + bwd, 32x2chx10s, fused={f}: median {ts[len(ts) // 2]:8.2f} ms  "
               f"(min {ts[0]:.2f}, max {ts[-1]:.2f}; {rounds} windows of {reps})", flush=True)
@@ -167,24 +177,30 @@ def run_msstft(rounds=5, reps=20):
     S = xs.numel() * 4
     med = sorted(times[True])[rounds // 2]
     print(f"fused path: {2 * 11 * S / 1e9:.2f} GB by its byte budget (11 S per scale) -> {2 * 11 * S / med / 1e6:.0f} GB/s end to end")
-    print("fused vs unfused grad rel diff", float((grads[True] - grads[False]).abs().max() / grads[False].abs().max()))
+    for f in MODES[1:]:
+        print(f"fused={f} vs unfused grad rel diff", float((grads[f] - grads[False]).abs().max() / grads[False].abs().max()))
 
     # the kernel alone (both scales, with and without G)
     from audiotools_amd import kernels
     for n_fft in (2048, 512):
         win = A.AudioSignal.get_window("hann", n_fft, str(xs.device))
-        for want in (True, False):
+        for want in (True, False, "dx", "G+adjoint"):
             call = lambda: kernels.stft_distance(xs, ys, win, n_fft, n_fft // 4, 1e-5, 2.0, 1e-9, 1e-9, want)
+            if want == "dx":
+                call = lambda: kernels.stft_distance_dx(xs, ys, win, n_fft, n_fft // 4, 1e-5, 2.0, 1e-9, 1e-9)
+            if want == "G+adjoint":     # what the waveform mode replaces: the G kernel, at_stft_adjoint_f32, the clone and the folds
+                call = lambda: kernels.stft_adjoint(kernels.stft_distance(xs, ys, win, n_fft, n_fft // 4, 1e-5, 2.0, 1e-9, 1e-9, True)[1],
+                                                    win, n_fft, n_fft // 4, xs.shape[-1])
             call()
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record()
-            for _ in range(10):
+            for _ in range(50):
                 call()
             t1.record()
             t1.synchronize()
-            ms = t0.elapsed_time(t1) / 10
-            nbytes = 2 * S + (4 * S if want else 0)
-            print(f"at_stft_dist_f32 n_fft={n_fft} G={want}: {ms:7.3f} ms, {nbytes / ms / 1e6:.0f} GB/s of its {nbytes / 1e9:.2f} GB", flush=True)
+            ms = t0.elapsed_time(t1) / 50
+            nbytes = 2 * S + {True: 4 * S, False: 0, "dx": S}.get(want, 12 * S)     # G+adjoint: 4 S out, 4 S in, ~4 S of OLA, clone, folds
+            print(f"at_stft_dist_f32 n_fft={n_fft} out={ {True: 'G', False: 'none'}.get(want, want) }: {ms:7.3f} ms, {nbytes / ms / 1e6:.0f} GB/s of its {nbytes / 1e9:.2f} GB", flush=True)
 
 
 if CASE in ("all", "msstft"):
