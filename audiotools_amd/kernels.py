@@ -757,6 +757,66 @@ def mel_distance_dx(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_ff
     return sums, dx
 
 
+def sisdr_supported(x, y) -> bool:
+    """The fused SI-SDR kernels (csrc/wavedist.hip) take this pair: two float32 HIP tensors of one shape on one device,
+    (B, ...) with 1 <= B <= 65535 items of 1 <= N < 2**31 samples."""
+    if not (torch.is_tensor(x) and torch.is_tensor(y) and x.is_cuda and y.is_cuda and x.dtype == y.dtype == torch.float32
+            and x.shape == y.shape and x.device == y.device and x.ndim >= 2 and 1 <= x.shape[0] <= 65535):
+        return False
+    return 1 <= x.numel() // x.shape[0] < 2 ** 31
+
+
+def _sisdr_rows(ref, est, what):
+    _require_native_ok(ref)
+    _require_native_ok(est)
+    if not sisdr_supported(ref, est):
+        raise ValueError(f"{what}: two float32 (B, ...) tensors of one shape on one device")
+    B = ref.shape[0]
+    return ref.contiguous(), est.contiguous(), B, ref.numel() // B
+
+
+def sisdr(ref: torch.Tensor, est: torch.Tensor, scaling: bool = True, zero_mean: bool = True, clip_min: float = None):
+    """Negative SI-SDR in dB per item of ``ref`` / ``est`` (B, ... float32 HIP tensors; ``ref`` is the FIRST argument of
+    ``SISDRLoss.forward``): one pass over both signals, float64 sums.
+
+    Returns ``(loss, coef, sums)``: ``loss`` (B, 1) float32; ``coef`` (B, 6) float32, the a, b, c of
+    d loss_b / d est = a est + b ref + c followed by those of d loss_b / d ref (what :func:`sisdr_grad` reads; zero where the
+    clamp is active); ``sums`` (B, 5) float64 = sum ref, sum est, sum ref^2, sum est^2, sum ref est.  Nothing is read back
+    to the host."""
+    ref, est, B, N = _sisdr_rows(ref, est, "sisdr")
+    dev = ref.device
+    lib = _native.lib()
+    nbytes = lib.at_sisdr_workspace_bytes(B, N)
+    _native.check(min(nbytes, 0), "at_sisdr_workspace_bytes")
+    ws = _workspace(nbytes, dev)
+    loss = torch.empty((B, 1), dtype=torch.float32, device=dev)
+    coef = torch.empty((B, 6), dtype=torch.float32, device=dev)
+    sums = torch.empty((B, 5), dtype=torch.float64, device=dev)
+    code = lib.at_sisdr_f32(_native.ptr(ref), _native.ptr(est), B, N, int(bool(scaling)), int(bool(zero_mean)),
+                            int(clip_min is not None), 0.0 if clip_min is None else float(clip_min), _native.ptr(loss),
+                            _native.ptr(coef), _native.ptr(sums), _native.ptr(ws), ws.numel(), _native.current_stream(dev))
+    _native.check(code, "at_sisdr_f32")
+    return loss, coef, sums
+
+
+def sisdr_grad(ref: torch.Tensor, est: torch.Tensor, coef: torch.Tensor, go: torch.Tensor, want_ref: bool, want_est: bool):
+    """Gradient of ``(go * loss).sum()`` of :func:`sisdr`: ``(d_ref, d_est)`` in the shape of the signals (None where not
+    wanted), both from one read of the two signals.  ``go`` = B float32 upstream gradients on the device."""
+    ref, est, B, N = _sisdr_rows(ref, est, "sisdr_grad")
+    dev = ref.device
+    if coef.shape != (B, 6) or coef.dtype != torch.float32 or coef.device != dev or not (want_ref or want_est):
+        raise ValueError("sisdr_grad: coef (B, 6) float32 of sisdr() and at least one output")
+    go = go.detach().to(device=dev, dtype=torch.float32).reshape(B).contiguous()
+    coef = coef.contiguous()
+    d_ref = _alloc_retry(lambda: torch.empty_like(ref)) if want_ref else None
+    d_est = _alloc_retry(lambda: torch.empty_like(est)) if want_est else None
+    code = _native.lib().at_sisdr_grad_f32(_native.ptr(ref), _native.ptr(est), B, N, _native.ptr(coef),
+                                           _native.ptr(go), _native.ptr(d_ref), _native.ptr(d_est),
+                                           _native.current_stream(dev))
+    _native.check(code, "at_sisdr_grad_f32")
+    return d_ref, d_est
+
+
 def istft_adjoint_supported(n_fft: int, hop: int) -> bool:
     return istft_fused_supported(n_fft, hop) and (n_fft // 2) % hop == 0 and stft_fused_supported(n_fft)
 

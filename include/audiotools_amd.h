@@ -214,6 +214,31 @@ int at_mel_dist_dx_f32(const float* x, const float* y, int64_t rows, int64_t T, 
                        float clamp_eps, float power, float g_log, float g_mag, float* dx, double* sums,
                        void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- fused SI-SDR loss: per-item loss and its gradient coefficients in one pass, gradient in one more ------
+ * Replaces  audiotools/metrics/distance.py:43-131  (SISDRLoss.forward: the centring, alpha, target, residual, the two
+ * energies, log10 and clamp -- a dozen passes over two (B, C*T) signals -- and their autograd replay).  ref is the FIRST
+ * argument of SISDRLoss.forward, est the second.  With Sr, Se, Srr, See, Sre the sums over one item of ref, est, ref^2,
+ * est^2, ref est (accumulated in float64 from the float32 samples), eps = 1e-8:
+ *   zero_mean: Crr = Srr - Sr^2/N, Cee = See - Se^2/N, Cre = Sre - Sr Se/N  (otherwise the raw sums)
+ *   alpha = scaling ? (Cre + eps) / (Crr + eps) : 1,   St = alpha^2 Crr,   Sres = Cee - 2 alpha Cre + St
+ *   loss  = max(-10 log10(St / Sres + eps), clip_min if has_clip)
+ *   ref, est  (rows, N) f32, row-contiguous; any 4-byte alignment
+ *   loss  (rows) f32;   sums (rows, 5) f64 = Sr, Se, Srr, See, Sre
+ *   coef  (rows, 6) f32 = a, b, c of  d loss_b / d est = a est + b ref + c,  then a, b, c of d loss_b / d ref; all zero where
+ *         the clamp is active.  Silent ref: loss 80; silence in both: NaN, as in the reference.
+ *   workspace at_sisdr_workspace_bytes(rows, N) bytes (a negative error for shapes the kernels do not take)
+ * at_sisdr_grad_f32:  d_est[b] = go[b] (a est + b ref + c) with the item's first three coefficients, d_ref[b] likewise with
+ *   the last three; go (rows) f32 on the DEVICE (no host synchronisation); a NULL output is not wanted (both NULL:
+ *   AT_ERR_INVALID); both outputs come from one read of the signals.
+ * 1 <= rows <= 65535, 1 <= N < 2^31 (AT_ERR_UNSUPPORTED above).  No atomics: equal inputs give equal bits on one device.
+ */
+int64_t at_sisdr_workspace_bytes(int64_t rows, int64_t N);
+int at_sisdr_f32(const float* ref, const float* est, int64_t rows, int64_t N, int scaling, int zero_mean, int has_clip,
+                 float clip_min, float* loss, float* coef, double* sums, void* workspace, int64_t workspace_bytes,
+                 void* stream);
+int at_sisdr_grad_f32(const float* ref, const float* est, int64_t rows, int64_t N, const float* coef, const float* go,
+                      float* d_ref, float* d_est, void* stream);
+
 /* ---- BS.1770 integrated loudness ---------------------------------------------------
  * Replaces  audiotools/core/loudness.py:102-126  (2x torchaudio.functional.lfilter, the
  *           CPU/IIR branch), :164-174 (julius.core.unfold), :176-247 (gated integration).

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Forward + backward of a magnitude loss through stft(): native kernels vs torch.stft autograd on the GPU.
 
-usage: gradbench.py [B [case]]    case: all (default) | stft | mel | dacmel | msstft"""
+usage: gradbench.py [B [case]]    case: all (default) | stft | mel | dacmel | msstft | sisdr (its own shapes, whatever B)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -205,3 +205,57 @@ def run_msstft(rounds=5, reps=20):
 
 if CASE in ("all", "msstft"):
     run_msstft()
+
+
+def _timed(call, reps):
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(reps):
+        call()
+    t1.record()
+    t1.synchronize()
+    return t0.elapsed_time(t1) / reps
+
+
+def run_sisdr(shape, rounds=7, reps=20):
+    """SISDRLoss forward + backward (gradient of the estimate), fused=True (csrc/wavedist.hip) against fused=False, alternating in
+    one process, every window timed with HIP events; then the two streaming kernels alone next to torch's copy_ of one signal."""
+    from audiotools_amd import kernels, metrics
+    g = torch.Generator(device="cuda").manual_seed(3)
+    ref = (0.1 * torch.randn(shape, device="cuda", generator=g)).clamp_(-1, 1)
+    est = 0.7 * ref + 0.01 * torch.randn(shape, device="cuda", generator=g)
+    losses = {f: metrics.distance.SISDRLoss(fused=f) for f in (False, True)}
+
+    def fn(fused):
+        ea = est.detach().requires_grad_(True)
+        loss = losses[fused](ref, ea)
+        loss.backward()
+        return loss.detach(), ea.grad
+
+    out = {f: fn(f) for f in (False, True)}         # warm-up of both paths
+    times = {f: [] for f in (False, True)}
+    for _ in range(rounds):
+        for f in (False, True):
+            times[f].append(_timed(lambda: fn(f), reps))
+    for f in (False, True):
+        ts = sorted(times[f])
+        print(f"SISDRLoss fwd + bwd {tuple(shape)}, fused={f}: median {ts[len(ts) // 2]:8.3f} ms  (min {ts[0]:.3f}, max {ts[-1]:.3f}; "
+              f"{rounds} windows of {reps})", flush=True)
+    print(f"loss fused {float(out[True][0]):.6f} unfused {float(out[False][0]):.6f}; grad rel diff "
+          f"{float((out[True][1] - out[False][1]).abs().max() / out[False][1].abs().max()):.2e}")
+    S = ref.numel() * 4
+    _, coef, _ = kernels.sisdr(ref, est)
+    go = torch.full((shape[0], 1), 1.0 / shape[0], device="cuda")
+    dst = torch.empty_like(ref)
+    for name, call, nbytes in (("sisdr sums + finish", lambda: kernels.sisdr(ref, est), 2 * S),
+                               ("sisdr grad (est)", lambda: kernels.sisdr_grad(ref, est, coef, go, False, True), 3 * S),
+                               ("sisdr grad (both)", lambda: kernels.sisdr_grad(ref, est, coef, go, True, True), 4 * S),
+                               ("torch copy_", lambda: dst.copy_(ref), 2 * S)):
+        call()
+        ts = sorted(_timed(call, 50) for _ in range(5))
+        print(f"{name} {tuple(shape)}: median {ts[2]:7.4f} ms, {nbytes / ts[2] / 1e6:.0f} GB/s of its {nbytes / 1e9:.4f} GB", flush=True)
+
+
+if CASE in ("all", "sisdr"):
+    for shape in ((64, 1, 441000), (8, 1, 16000)):
+        run_sisdr(shape)
