@@ -156,6 +156,10 @@ SIGNATURES = {
     "at_mel_dist_dx_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32]),
     "at_mel_dist_dx_f32": (_i32, [_p, _p, _i64, _i64, _p, _p, _i32, _i32, _p, _p, _p, _i32, _f32, _f32, _f32, _f32, _p, _p, _p, _i64, _p]),
     "at_mel_dist_f32": (_i32, [_p, _p, _i64, _i64, _p, _p, _i32, _i32, _p, _p, _p, _i32, _f32, _f32, _f32, _f32, _p, _p, _p, _i64, _p]),
+    "at_stft_dist_l2_f32": (_i32, [_p, _p, _i64, _i64, _p, _p, _i32, _i32, _f32, _f32, _f32, _f32, _p, _p, _p, _i64, _p]),
+    "at_stft_dist_dx_l2_f32": (_i32, [_p, _p, _i64, _i64, _p, _p, _i32, _i32, _f32, _f32, _f32, _f32, _p, _p, _p, _i64, _p]),
+    "at_mel_dist_l2_f32": (_i32, [_p, _p, _i64, _i64, _p, _p, _i32, _i32, _p, _p, _p, _i32, _f32, _f32, _f32, _f32, _p, _p, _p, _i64, _p]),
+    "at_mel_dist_dx_l2_f32": (_i32, [_p, _p, _i64, _i64, _p, _p, _i32, _i32, _p, _p, _p, _i32, _f32, _f32, _f32, _f32, _p, _p, _p, _i64, _p]),
     "at_sisdr_workspace_bytes": (_i64, [_i64, _i64]),
     "at_sisdr_f32": (_i32, [_p, _p, _i64, _i64, _i32, _i32, _i32, _f32, _p, _p, _p, _p, _i64, _p]),
     "at_sisdr_grad_f32": (_i32, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p]),

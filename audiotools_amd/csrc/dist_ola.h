@@ -32,6 +32,7 @@
 namespace {
 
 enum DistMode { DIST_NONE = 0, DIST_G = 1, DIST_DX = 2 };   // what a distance kernel produces besides the two sums
+enum DistLoss { LOSS_L1 = 0, LOSS_L2 = 1 };                 // how a distance kernel compares: |d| (nn.L1Loss) or d^2 (nn.MSELoss)
 
 struct OlaOut {
   float* dx;         // (rows, T)

@@ -1,6 +1,6 @@
 // Fused mel-spectrogram distance for gfx950: loss sums and dL/dX of ONE scale in one kernel.
 //
-// Replaces, per scale of  reference audiotools/metrics/spectral.py:97-194  (MelSpectrogramLoss with an L1 loss_fn):
+// Replaces, per scale of  reference audiotools/metrics/spectral.py:97-194  (MelSpectrogramLoss with an L1 or an MSE loss_fn):
 //   two mel_spectrogram() calls (each writes a full spectrum), clamp / pow / log10 / sub / abs / mean on both mel tensors,
 //   the autograd replay of all of them and the read-back of the saved spectrum in the mel adjoint.
 // The distance is a function of two SIGNALS: the kernel reads x and y once, keeps both mel rows on chip, and the only large
@@ -23,7 +23,10 @@
 //  * two float accumulators per lane over the run, one wave reduction, one partial pair per wave; a one-workgroup kernel adds
 //    the partials in double in a fixed order: no atomics, bit-equal sums and G on every run;
 //  * MODE: DIST_NONE (sums), DIST_G (sums and G, above), DIST_DX (sums and the gradient of the SIGNAL: G stays in the slab and
-//    goes through the adjoint transform and the in-wave overlap-add of dist_ola.h; at_mel_dist_dx_f32).
+//    goes through the adjoint transform and the in-wave overlap-add of dist_ola.h; at_mel_dist_dx_f32);
+//  * LOSS: LOSS_L1 (absolute differences, dL/dmel from their signs) or LOSS_L2 (squared differences, dL/dmel from the
+//    differences themselves: nn.MSELoss; at_mel_dist_l2_f32, at_mel_dist_dx_l2_f32).  A template parameter: only the band
+//    comparison differs; the band walk, the back-projection and everything after dL/dmel are those of LOSS_L1.
 #include "at_common.h"
 #include "fft_wave.h"
 #include "dist_ola.h"
@@ -55,7 +58,7 @@ struct MelArgs {
   int n_mels;
   float eps;               // clamp of mel (not of its square)
   float c_log;             // power * log10(2):  c_log * log2(mel) = power * log10 mel
-  float g_logp;            // g_log * power / ln 10
+  float g_logp;            // g_log * power / ln 10   (LOSS_L2: times 2, and so is g_mag)
   float g_mag;
   int vec2;                // rows of x and y are 8-byte aligned: float2 loads
   OlaOut ola;              // DIST_DX only: where the waveform gradient goes (dist_ola.h)
@@ -73,7 +76,7 @@ constexpr int lds_floats(int mode) {
 __device__ __forceinline__ float abs2(float2 z) { return fmaf(z.x, z.x, z.y * z.y); }
 __device__ __forceinline__ float sgnf(float a, float b) { return (a > b ? 1.f : 0.f) - (a < b ? 1.f : 0.f); }
 
-template <int M, int MODE>
+template <int M, int MODE, int LOSS>
 __global__ __launch_bounds__(NW * 64, 2) void mel_dist_kernel(const MelArgs A) {
   constexpr bool GRAD = MODE != DIST_NONE;
   using P = Plan<M>;
@@ -305,12 +308,24 @@ __global__ __launch_bounds__(NW * 64, 2) void mel_dist_kernel(const MelArgs A) {
         const bool on = valid && m < A.n_mels;
         const float a = mx[j], b = my[j];
         const float la = A.c_log * __builtin_amdgcn_logf(fmaxf(a, A.eps));
-        s_log += on ? fabsf(la - ly[j]) : 0.f;
-        s_mag += on ? fabsf(a - b) : 0.f;
-        if constexpr (GRAD) {
-          const float sl = sgnf(fmaxf(a, A.eps), fmaxf(b, A.eps));
-          const float gl = a >= A.eps ? A.g_logp * sl * __builtin_amdgcn_rcpf(a) : 0.f;
-          if (m < A.n_mels) grow[m] = fmaf(A.g_mag, sgnf(a, b), gl);
+        if constexpr (LOSS == LOSS_L2) {
+          // squared error: the differences take the place of their signs (A.g_logp and A.g_mag carry the factor 2); below
+          // the clamp la is the constant p log10 eps, so the [a >= eps] select is all the clamp needs
+          const float dl = la - ly[j], dm = a - b;
+          s_log += on ? dl * dl : 0.f;
+          s_mag += on ? dm * dm : 0.f;
+          if constexpr (GRAD) {
+            const float gl = a >= A.eps ? A.g_logp * dl * __builtin_amdgcn_rcpf(a) : 0.f;
+            if (m < A.n_mels) grow[m] = fmaf(A.g_mag, dm, gl);
+          }
+        } else {
+          s_log += on ? fabsf(la - ly[j]) : 0.f;
+          s_mag += on ? fabsf(a - b) : 0.f;
+          if constexpr (GRAD) {
+            const float sl = sgnf(fmaxf(a, A.eps), fmaxf(b, A.eps));
+            const float gl = a >= A.eps ? A.g_logp * sl * __builtin_amdgcn_rcpf(a) : 0.f;
+            if (m < A.n_mels) grow[m] = fmaf(A.g_mag, sgnf(a, b), gl);
+          }
         }
       }
       if constexpr (GRAD) {
@@ -397,9 +412,9 @@ __global__ __launch_bounds__(256) void mel_dist_finalize(const float2* __restric
   }
 }
 
-template <int M, int MODE>
+template <int M, int MODE, int LOSS>
 int launch_one(const MelArgs& A, int blocks, hipStream_t stream) {
-  auto kern = mel_dist_kernel<M, MODE>;
+  auto kern = mel_dist_kernel<M, MODE, LOSS>;
   // n_fft 2048: 71948 B with G (two workgroups per CU), 96524 B in waveform mode (one workgroup per CU)
   const size_t bytes = (size_t)lds_floats<M>(MODE) * 4;
   if (bytes > 64 * 1024) {
@@ -411,10 +426,15 @@ int launch_one(const MelArgs& A, int blocks, hipStream_t stream) {
   return AT_OK;
 }
 
+template <int M, int LOSS>
+int launch_loss(const MelArgs& A, int blocks, hipStream_t stream) {
+  if (A.ola.dx) return launch_one<M, DIST_DX, LOSS>(A, blocks, stream);
+  return A.G ? launch_one<M, DIST_G, LOSS>(A, blocks, stream) : launch_one<M, DIST_NONE, LOSS>(A, blocks, stream);
+}
+
 template <int M>
-int launch_mel(const MelArgs& A, int blocks, hipStream_t stream) {
-  if (A.ola.dx) return launch_one<M, DIST_DX>(A, blocks, stream);
-  return A.G ? launch_one<M, DIST_G>(A, blocks, stream) : launch_one<M, DIST_NONE>(A, blocks, stream);
+int launch_mel(const MelArgs& A, int loss, int blocks, hipStream_t stream) {
+  return loss == LOSS_L2 ? launch_loss<M, LOSS_L2>(A, blocks, stream) : launch_loss<M, LOSS_L1>(A, blocks, stream);
 }
 
 // AT_OK when the kernel takes the shape
@@ -443,7 +463,7 @@ int64_t dx_max_blocks(int64_t rows, int64_t T, int n_fft, int hop) {
 }
 
 // G != null: dL/dX; dx != null: dL/dx through the overlap-add tail (workspace: partials, seam slots, margins)
-int mel_run(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles, int n_fft,
+int mel_run(int loss, const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles, int n_fft,
             int hop, const int* bin_bands, const float* bin_w, const int* band_span, int n_mels, float clamp_eps, float power,
             float g_log, float g_mag, float* G, float* dx, double* sums, void* workspace, hipStream_t s) {
   const int M = n_fft / 2, FW = 64 / (M / 16);
@@ -457,8 +477,10 @@ int mel_run(const float* x, const float* y, int64_t rows, int64_t T, const float
   A.n_mels = n_mels;
   A.eps = clamp_eps;
   A.c_log = (float)((double)power * 0.30102999566398119521);
-  A.g_logp = (float)((double)g_log * (double)power / 2.30258509299404568402);
-  A.g_mag = g_mag;
+  // LOSS_L2: d (la - lb)^2 = 2 (la - lb) d la, d (a - b)^2 = 2 (a - b) d a -- the 2 (exact) rides on the weights
+  const double two = loss == LOSS_L2 ? 2.0 : 1.0;
+  A.g_logp = (float)(two * (double)g_log * (double)power / 2.30258509299404568402);
+  A.g_mag = (float)(two * (double)g_mag);
   A.vec2 = ((T % 2) == 0 && (reinterpret_cast<uintptr_t>(x) % 8) == 0 && (reinterpret_cast<uintptr_t>(y) % 8) == 0) ? 1 : 0;
   int64_t blocks = mel_max_blocks(rows, T, n_fft, hop);
   const int64_t resident = mel_resident(n_fft, dx != nullptr);
@@ -476,13 +498,13 @@ int mel_run(const float* x, const float* y, int64_t rows, int64_t T, const float
   }
   int r = AT_ERR_UNSUPPORTED;
   switch (M) {
-    case 16: r = launch_mel<16>(A, (int)blocks, s); break;
-    case 32: r = launch_mel<32>(A, (int)blocks, s); break;
-    case 64: r = launch_mel<64>(A, (int)blocks, s); break;
-    case 128: r = launch_mel<128>(A, (int)blocks, s); break;
-    case 256: r = launch_mel<256>(A, (int)blocks, s); break;
-    case 512: r = launch_mel<512>(A, (int)blocks, s); break;
-    case 1024: r = launch_mel<1024>(A, (int)blocks, s); break;
+    case 16: r = launch_mel<16>(A, loss, (int)blocks, s); break;
+    case 32: r = launch_mel<32>(A, loss, (int)blocks, s); break;
+    case 64: r = launch_mel<64>(A, loss, (int)blocks, s); break;
+    case 128: r = launch_mel<128>(A, loss, (int)blocks, s); break;
+    case 256: r = launch_mel<256>(A, loss, (int)blocks, s); break;
+    case 512: r = launch_mel<512>(A, loss, (int)blocks, s); break;
+    case 1024: r = launch_mel<1024>(A, loss, (int)blocks, s); break;
   }
   if (r != AT_OK) return r;
   if (dx) {
@@ -506,17 +528,34 @@ int64_t at_mel_dist_workspace_bytes(int64_t rows, int64_t T, int n_fft, int hop,
   return mel_max_blocks(rows, T, n_fft, hop) * NW * (int64_t)sizeof(float2);
 }
 
-int at_mel_dist_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
-                    int n_fft, int hop, const int* bin_bands, const float* bin_w, const int* band_span, int n_mels,
-                    float clamp_eps, float power, float g_log, float g_mag, float* G, double* sums,
-                    void* workspace, int64_t workspace_bytes, void* stream) {
+// the checks and the launch of at_mel_dist_f32 / at_mel_dist_l2_f32
+static int mel_entry(int loss, const float* x, const float* y, int64_t rows, int64_t T, const float* window,
+                     const float* twiddles, int n_fft, int hop, const int* bin_bands, const float* bin_w, const int* band_span,
+                     int n_mels, float clamp_eps, float power, float g_log, float g_mag, float* G, double* sums,
+                     void* workspace, int64_t workspace_bytes, void* stream) {
   if (!x || !y || !window || !twiddles || !bin_bands || !bin_w || !band_span || !sums || !workspace) return AT_ERR_INVALID;
   const int e = mel_shape_check(rows, T, n_fft, hop, n_mels);
   if (e != AT_OK) return e;
   if (!(clamp_eps >= FLT_MIN) || !(power > 0.f)) return AT_ERR_UNSUPPORTED;
   if (workspace_bytes < at_mel_dist_workspace_bytes(rows, T, n_fft, hop, n_mels)) return AT_ERR_INVALID;
-  return mel_run(x, y, rows, T, window, twiddles, n_fft, hop, bin_bands, bin_w, band_span, n_mels, clamp_eps, power, g_log,
-                 g_mag, G, nullptr, sums, workspace, reinterpret_cast<hipStream_t>(stream));
+  return mel_run(loss, x, y, rows, T, window, twiddles, n_fft, hop, bin_bands, bin_w, band_span, n_mels, clamp_eps, power,
+                 g_log, g_mag, G, nullptr, sums, workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
+int at_mel_dist_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                    int n_fft, int hop, const int* bin_bands, const float* bin_w, const int* band_span, int n_mels,
+                    float clamp_eps, float power, float g_log, float g_mag, float* G, double* sums,
+                    void* workspace, int64_t workspace_bytes, void* stream) {
+  return mel_entry(LOSS_L1, x, y, rows, T, window, twiddles, n_fft, hop, bin_bands, bin_w, band_span, n_mels, clamp_eps, power,
+                   g_log, g_mag, G, sums, workspace, workspace_bytes, stream);
+}
+
+int at_mel_dist_l2_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                       int n_fft, int hop, const int* bin_bands, const float* bin_w, const int* band_span, int n_mels,
+                       float clamp_eps, float power, float g_log, float g_mag, float* G, double* sums,
+                       void* workspace, int64_t workspace_bytes, void* stream) {
+  return mel_entry(LOSS_L2, x, y, rows, T, window, twiddles, n_fft, hop, bin_bands, bin_w, band_span, n_mels, clamp_eps, power,
+                   g_log, g_mag, G, sums, workspace, workspace_bytes, stream);
 }
 
 // partials (a float2 per wave), seam slots (3 hops per wave), margins (rows x n_fft)
@@ -527,17 +566,34 @@ int64_t at_mel_dist_dx_workspace_bytes(int64_t rows, int64_t T, int n_fft, int h
   return (waves * (2 + 3 * (int64_t)hop) + rows * n_fft) * (int64_t)sizeof(float);
 }
 
-int at_mel_dist_dx_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
-                       int n_fft, int hop, const int* bin_bands, const float* bin_w, const int* band_span, int n_mels,
-                       float clamp_eps, float power, float g_log, float g_mag, float* dx, double* sums,
-                       void* workspace, int64_t workspace_bytes, void* stream) {
+// the checks and the launch of at_mel_dist_dx_f32 / at_mel_dist_dx_l2_f32
+static int mel_dx_entry(int loss, const float* x, const float* y, int64_t rows, int64_t T, const float* window,
+                        const float* twiddles, int n_fft, int hop, const int* bin_bands, const float* bin_w,
+                        const int* band_span, int n_mels, float clamp_eps, float power, float g_log, float g_mag, float* dx,
+                        double* sums, void* workspace, int64_t workspace_bytes, void* stream) {
   if (!x || !y || !window || !twiddles || !bin_bands || !bin_w || !band_span || !dx || !sums || !workspace) return AT_ERR_INVALID;
   const int e = mel_shape_check(rows, T, n_fft, hop, n_mels);
   if (e != AT_OK) return e;
   if (!(clamp_eps >= FLT_MIN) || !(power > 0.f)) return AT_ERR_UNSUPPORTED;
   if (workspace_bytes < at_mel_dist_dx_workspace_bytes(rows, T, n_fft, hop, n_mels)) return AT_ERR_INVALID;
-  return mel_run(x, y, rows, T, window, twiddles, n_fft, hop, bin_bands, bin_w, band_span, n_mels, clamp_eps, power, g_log,
-                 g_mag, nullptr, dx, sums, workspace, reinterpret_cast<hipStream_t>(stream));
+  return mel_run(loss, x, y, rows, T, window, twiddles, n_fft, hop, bin_bands, bin_w, band_span, n_mels, clamp_eps, power,
+                 g_log, g_mag, nullptr, dx, sums, workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
+int at_mel_dist_dx_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                       int n_fft, int hop, const int* bin_bands, const float* bin_w, const int* band_span, int n_mels,
+                       float clamp_eps, float power, float g_log, float g_mag, float* dx, double* sums,
+                       void* workspace, int64_t workspace_bytes, void* stream) {
+  return mel_dx_entry(LOSS_L1, x, y, rows, T, window, twiddles, n_fft, hop, bin_bands, bin_w, band_span, n_mels, clamp_eps,
+                      power, g_log, g_mag, dx, sums, workspace, workspace_bytes, stream);
+}
+
+int at_mel_dist_dx_l2_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                          int n_fft, int hop, const int* bin_bands, const float* bin_w, const int* band_span, int n_mels,
+                          float clamp_eps, float power, float g_log, float g_mag, float* dx, double* sums,
+                          void* workspace, int64_t workspace_bytes, void* stream) {
+  return mel_dx_entry(LOSS_L2, x, y, rows, T, window, twiddles, n_fft, hop, bin_bands, bin_w, band_span, n_mels, clamp_eps,
+                      power, g_log, g_mag, dx, sums, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // Fused multi-scale STFT distance for gfx950: loss sums and dL/dX of ONE scale in one kernel.
 //
-// Replaces, per scale of  reference audiotools/metrics/spectral.py:11-94  (MultiScaleSTFTLoss with an L1 loss_fn):
+// Replaces, per scale of  reference audiotools/metrics/spectral.py:11-94  (MultiScaleSTFTLoss with an L1 or an MSE loss_fn):
 //   two stft() calls, abs / clamp / pow / log10 / sub / abs / mean on both spectra, and the autograd replay of all of them.
 // The distance is a function of two SIGNALS: the kernel reads x and y once, never writes a spectrum of either, and the only
 // large object it produces is G = dL/dX (when a gradient is wanted), in the layout at_stft_adjoint_f32 reads.
@@ -20,7 +20,10 @@
 //    a one-workgroup kernel adds the partials in double in a fixed order: no atomics, bit-equal sums on every run;
 //  * frame slots past a row's last frame repeat that frame (as in stft.hip) but add nothing and store nothing;
 //  * MODE: DIST_NONE (sums), DIST_G (sums and G, above), DIST_DX (sums and the gradient of the SIGNAL: G stays in the slab and
-//    goes through the adjoint transform and the in-wave overlap-add of dist_ola.h; at_stft_dist_dx_f32).
+//    goes through the adjoint transform and the in-wave overlap-add of dist_ola.h; at_stft_dist_dx_f32);
+//  * LOSS: LOSS_L1 (absolute differences, gradient from their signs) or LOSS_L2 (squared differences, gradient from the
+//    differences themselves: nn.MSELoss; at_stft_dist_l2_f32, at_stft_dist_dx_l2_f32).  A template parameter: only the bin
+//    comparison differs, the target-side registers, the slab traffic and the reductions are those of LOSS_L1.
 #include "at_common.h"
 #include "fft_wave.h"
 #include "dist_ola.h"
@@ -47,7 +50,7 @@ struct DistArgs {
   int64_t total_groups;    // rows * gpr
   float eps, eps2;         // clamp_eps and its square
   float c_log;             // 0.5 * power * log10(2):  c_log * log2(|X|^2) = power * log10 |X|
-  float g_logp;            // g_log * power / ln 10
+  float g_logp;            // g_log * power / ln 10   (LOSS_L2: times 2, and so is g_mag)
   float g_mag;
   int vec2;                // rows of x and y are 8-byte aligned: float2 loads
   OlaOut ola;              // DIST_DX only: where the waveform gradient goes (dist_ola.h)
@@ -62,7 +65,7 @@ constexpr int lds_floats(int mode = DIST_NONE) {
 __device__ __forceinline__ float abs2(float2 z) { return fmaf(z.x, z.x, z.y * z.y); }
 __device__ __forceinline__ float sgnf(float a, float b) { return (a > b ? 1.f : 0.f) - (a < b ? 1.f : 0.f); }
 
-template <int M, int MODE>
+template <int M, int MODE, int LOSS>
 __global__ __launch_bounds__(NW * 64, 2) void stft_dist_kernel(const DistArgs A) {
   constexpr bool GRAD = MODE != DIST_NONE;
   using P = Plan<M>;
@@ -243,15 +246,28 @@ __global__ __launch_bounds__(NW * 64, 2) void stft_dist_kernel(const DistArgs A)
       const float a2 = abs2(X);
       const float a = __builtin_amdgcn_sqrtf(a2);
       const float la = A.c_log * __builtin_amdgcn_logf(fmaxf(a2, A.eps2));
-      s_log += on ? fabsf(la - lb) : 0.f;
-      s_mag += on ? fabsf(a - b) : 0.f;
-      if constexpr (!GRAD) return X;
-      // 1/|X|; G = 0 where |X|^2 is zero (or below the normal range, where v_rsq_f32 is not defined)
-      const float inv = a2 >= FLT_MIN ? __builtin_amdgcn_rsqf(a2) : 0.f;
-      const float sl = sgnf(fmaxf(a, A.eps), fmaxf(b, A.eps));
-      const float gl = a >= A.eps ? A.g_logp * sl * inv : 0.f;
-      const float coef = fmaf(A.g_mag, sgnf(a, b), gl) * inv;
-      return make_float2(coef * X.x, coef * X.y);
+      if constexpr (LOSS == LOSS_L2) {
+        // squared error: the differences take the place of their signs (A.g_logp and A.g_mag carry the factor 2); below
+        // the clamp la is the constant p log10 eps, so the [a >= eps] select is all the clamp needs
+        const float dl = la - lb, dm = a - b;
+        s_log += on ? dl * dl : 0.f;
+        s_mag += on ? dm * dm : 0.f;
+        if constexpr (!GRAD) return X;
+        const float inv = a2 >= FLT_MIN ? __builtin_amdgcn_rsqf(a2) : 0.f;
+        const float gl = a >= A.eps ? A.g_logp * dl * inv : 0.f;
+        const float coef = fmaf(A.g_mag, dm, gl) * inv;
+        return make_float2(coef * X.x, coef * X.y);
+      } else {
+        s_log += on ? fabsf(la - lb) : 0.f;
+        s_mag += on ? fabsf(a - b) : 0.f;
+        if constexpr (!GRAD) return X;
+        // 1/|X|; G = 0 where |X|^2 is zero (or below the normal range, where v_rsq_f32 is not defined)
+        const float inv = a2 >= FLT_MIN ? __builtin_amdgcn_rsqf(a2) : 0.f;
+        const float sl = sgnf(fmaxf(a, A.eps), fmaxf(b, A.eps));
+        const float gl = a >= A.eps ? A.g_logp * sl * inv : 0.f;
+        const float coef = fmaf(A.g_mag, sgnf(a, b), gl) * inv;
+        return make_float2(coef * X.x, coef * X.y);
+      }
     };
     {
       float2 xa[8], xb[8], xh;
@@ -328,9 +344,9 @@ __global__ __launch_bounds__(256) void stft_dist_finalize(const float2* __restri
   }
 }
 
-template <int M, int MODE>
+template <int M, int MODE, int LOSS>
 int launch_mode(const DistArgs& A, int blocks, hipStream_t stream) {
-  auto kern = stft_dist_kernel<M, MODE>;
+  auto kern = stft_dist_kernel<M, MODE, LOSS>;
   const size_t bytes = (size_t)lds_floats<M>(MODE) * 4;   // <= 49408 B; DIST_DX at n_fft 2048: 73984 B, still two workgroups per CU
   if (bytes > 64 * 1024) {
     const int e = at::allow_big_lds(reinterpret_cast<const void*>(kern));
@@ -341,10 +357,15 @@ int launch_mode(const DistArgs& A, int blocks, hipStream_t stream) {
   return AT_OK;
 }
 
+template <int M, int LOSS>
+int launch_loss(const DistArgs& A, int blocks, hipStream_t stream) {
+  if (A.ola.dx) return launch_mode<M, DIST_DX, LOSS>(A, blocks, stream);
+  return A.G ? launch_mode<M, DIST_G, LOSS>(A, blocks, stream) : launch_mode<M, DIST_NONE, LOSS>(A, blocks, stream);
+}
+
 template <int M>
-int launch_dist(const DistArgs& A, int blocks, hipStream_t stream) {
-  if (A.ola.dx) return launch_mode<M, DIST_DX>(A, blocks, stream);
-  return A.G ? launch_mode<M, DIST_G>(A, blocks, stream) : launch_mode<M, DIST_NONE>(A, blocks, stream);
+int launch_dist(const DistArgs& A, int loss, int blocks, hipStream_t stream) {
+  return loss == LOSS_L2 ? launch_loss<M, LOSS_L2>(A, blocks, stream) : launch_loss<M, LOSS_L1>(A, blocks, stream);
 }
 
 // AT_OK when the kernel takes the shape
@@ -371,8 +392,8 @@ int64_t dx_max_blocks(int64_t rows, int64_t T, int n_fft, int hop) {
 }
 
 // G != null: dL/dX; dx != null: dL/dx through the overlap-add tail (workspace: partials, seam slots, margins)
-int dist_run(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles, int n_fft,
-             int hop, float clamp_eps, float power, float g_log, float g_mag, float* G, float* dx, double* sums,
+int dist_run(int loss, const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+             int n_fft, int hop, float clamp_eps, float power, float g_log, float g_mag, float* G, float* dx, double* sums,
              void* workspace, hipStream_t s) {
   const int M = n_fft / 2, FW = 64 / (M / 16);
   DistArgs A;
@@ -383,8 +404,10 @@ int dist_run(const float* x, const float* y, int64_t rows, int64_t T, const floa
   A.total_groups = rows * A.gpr;
   A.eps = clamp_eps; A.eps2 = clamp_eps * clamp_eps;
   A.c_log = (float)(0.5 * (double)power * 0.30102999566398119521);
-  A.g_logp = (float)((double)g_log * (double)power / 2.30258509299404568402);
-  A.g_mag = g_mag;
+  // LOSS_L2: d (la - lb)^2 = 2 (la - lb) d la, d (a - b)^2 = 2 (a - b) d a -- the 2 (exact) rides on the weights
+  const double two = loss == LOSS_L2 ? 2.0 : 1.0;
+  A.g_logp = (float)(two * (double)g_log * (double)power / 2.30258509299404568402);
+  A.g_mag = (float)(two * (double)g_mag);
   A.vec2 = ((T % 2) == 0 && (reinterpret_cast<uintptr_t>(x) % 8) == 0 && (reinterpret_cast<uintptr_t>(y) % 8) == 0) ? 1 : 0;
   int64_t blocks = dist_max_blocks(rows, T, n_fft, hop);
   const int64_t resident = 2 * (int64_t)at::device_cu_count();      // two workgroups per CU (launch bounds; 49 KB / 74 KB of LDS each)
@@ -402,13 +425,13 @@ int dist_run(const float* x, const float* y, int64_t rows, int64_t T, const floa
   }
   int r = AT_ERR_UNSUPPORTED;
   switch (M) {
-    case 16: r = launch_dist<16>(A, (int)blocks, s); break;
-    case 32: r = launch_dist<32>(A, (int)blocks, s); break;
-    case 64: r = launch_dist<64>(A, (int)blocks, s); break;
-    case 128: r = launch_dist<128>(A, (int)blocks, s); break;
-    case 256: r = launch_dist<256>(A, (int)blocks, s); break;
-    case 512: r = launch_dist<512>(A, (int)blocks, s); break;
-    case 1024: r = launch_dist<1024>(A, (int)blocks, s); break;
+    case 16: r = launch_dist<16>(A, loss, (int)blocks, s); break;
+    case 32: r = launch_dist<32>(A, loss, (int)blocks, s); break;
+    case 64: r = launch_dist<64>(A, loss, (int)blocks, s); break;
+    case 128: r = launch_dist<128>(A, loss, (int)blocks, s); break;
+    case 256: r = launch_dist<256>(A, loss, (int)blocks, s); break;
+    case 512: r = launch_dist<512>(A, loss, (int)blocks, s); break;
+    case 1024: r = launch_dist<1024>(A, loss, (int)blocks, s); break;
   }
   if (r != AT_OK) return r;
   if (dx) {
@@ -432,16 +455,31 @@ int64_t at_stft_dist_workspace_bytes(int64_t rows, int64_t T, int n_fft, int hop
   return dist_max_blocks(rows, T, n_fft, hop) * NW * (int64_t)sizeof(float2);
 }
 
-int at_stft_dist_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
-                     int n_fft, int hop, float clamp_eps, float power, float g_log, float g_mag, float* G, double* sums,
-                     void* workspace, int64_t workspace_bytes, void* stream) {
+// the checks and the launch of at_stft_dist_f32 / at_stft_dist_l2_f32
+static int dist_entry(int loss, const float* x, const float* y, int64_t rows, int64_t T, const float* window,
+                      const float* twiddles, int n_fft, int hop, float clamp_eps, float power, float g_log, float g_mag,
+                      float* G, double* sums, void* workspace, int64_t workspace_bytes, void* stream) {
   if (!x || !y || !window || !twiddles || !sums || !workspace) return AT_ERR_INVALID;
   const int e = dist_shape_check(rows, T, n_fft, hop);
   if (e != AT_OK) return e;
   if (!(clamp_eps * clamp_eps >= FLT_MIN) || !(power > 0.f)) return AT_ERR_UNSUPPORTED;
   if (workspace_bytes < at_stft_dist_workspace_bytes(rows, T, n_fft, hop)) return AT_ERR_INVALID;
-  return dist_run(x, y, rows, T, window, twiddles, n_fft, hop, clamp_eps, power, g_log, g_mag, G, nullptr, sums, workspace,
-                  reinterpret_cast<hipStream_t>(stream));
+  return dist_run(loss, x, y, rows, T, window, twiddles, n_fft, hop, clamp_eps, power, g_log, g_mag, G, nullptr, sums,
+                  workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
+int at_stft_dist_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                     int n_fft, int hop, float clamp_eps, float power, float g_log, float g_mag, float* G, double* sums,
+                     void* workspace, int64_t workspace_bytes, void* stream) {
+  return dist_entry(LOSS_L1, x, y, rows, T, window, twiddles, n_fft, hop, clamp_eps, power, g_log, g_mag, G, sums, workspace,
+                    workspace_bytes, stream);
+}
+
+int at_stft_dist_l2_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                        int n_fft, int hop, float clamp_eps, float power, float g_log, float g_mag, float* G, double* sums,
+                        void* workspace, int64_t workspace_bytes, void* stream) {
+  return dist_entry(LOSS_L2, x, y, rows, T, window, twiddles, n_fft, hop, clamp_eps, power, g_log, g_mag, G, sums, workspace,
+                    workspace_bytes, stream);
 }
 
 // partials (a float2 per wave), seam slots (3 hops per wave), margins (rows x n_fft)
@@ -452,16 +490,31 @@ int64_t at_stft_dist_dx_workspace_bytes(int64_t rows, int64_t T, int n_fft, int 
   return (waves * (2 + 3 * (int64_t)hop) + rows * n_fft) * (int64_t)sizeof(float);
 }
 
-int at_stft_dist_dx_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
-                        int n_fft, int hop, float clamp_eps, float power, float g_log, float g_mag, float* dx, double* sums,
-                        void* workspace, int64_t workspace_bytes, void* stream) {
+// the checks and the launch of at_stft_dist_dx_f32 / at_stft_dist_dx_l2_f32
+static int dist_dx_entry(int loss, const float* x, const float* y, int64_t rows, int64_t T, const float* window,
+                         const float* twiddles, int n_fft, int hop, float clamp_eps, float power, float g_log, float g_mag,
+                         float* dx, double* sums, void* workspace, int64_t workspace_bytes, void* stream) {
   if (!x || !y || !window || !twiddles || !dx || !sums || !workspace) return AT_ERR_INVALID;
   const int e = dist_shape_check(rows, T, n_fft, hop);
   if (e != AT_OK) return e;
   if (!(clamp_eps * clamp_eps >= FLT_MIN) || !(power > 0.f)) return AT_ERR_UNSUPPORTED;
   if (workspace_bytes < at_stft_dist_dx_workspace_bytes(rows, T, n_fft, hop)) return AT_ERR_INVALID;
-  return dist_run(x, y, rows, T, window, twiddles, n_fft, hop, clamp_eps, power, g_log, g_mag, nullptr, dx, sums, workspace,
-                  reinterpret_cast<hipStream_t>(stream));
+  return dist_run(loss, x, y, rows, T, window, twiddles, n_fft, hop, clamp_eps, power, g_log, g_mag, nullptr, dx, sums,
+                  workspace, reinterpret_cast<hipStream_t>(stream));
+}
+
+int at_stft_dist_dx_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                        int n_fft, int hop, float clamp_eps, float power, float g_log, float g_mag, float* dx, double* sums,
+                        void* workspace, int64_t workspace_bytes, void* stream) {
+  return dist_dx_entry(LOSS_L1, x, y, rows, T, window, twiddles, n_fft, hop, clamp_eps, power, g_log, g_mag, dx, sums,
+                       workspace, workspace_bytes, stream);
+}
+
+int at_stft_dist_dx_l2_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window,
+                           const float* twiddles, int n_fft, int hop, float clamp_eps, float power, float g_log, float g_mag,
+                           float* dx, double* sums, void* workspace, int64_t workspace_bytes, void* stream) {
+  return dist_dx_entry(LOSS_L2, x, y, rows, T, window, twiddles, n_fft, hop, clamp_eps, power, g_log, g_mag, dx, sums,
+                       workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

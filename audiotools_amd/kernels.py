@@ -610,22 +610,35 @@ def stft_mel_adjoint(X_bcfn: torch.Tensor, gmel_bcmn: torch.Tensor, bin_table, w
     return _fold_reflect(out, T, half)
 
 
-def stft_distance_supported(n_fft: int, hop: int, T: int, clamp_eps: float, power: float) -> bool:
+def _dist_entry(name: str, loss: str) -> str:
+    """Entry point of a fused distance launch for ``loss``: "l1" (absolute differences) or "l2" (squared differences)."""
+    if loss not in ("l1", "l2"):
+        raise ValueError(f'loss must be "l1" or "l2", not {loss!r}')
+    return name if loss == "l1" else name.replace("_f32", "_l2_f32")
+
+
+def stft_distance_supported(n_fft: int, hop: int, T: int, clamp_eps: float, power: float, loss: str = "l1") -> bool:
     """The fused distance kernel (csrc/stftdist.hip) takes this scale: power-of-two n_fft in 32 ... 2048, hop = n_fft / 4,
-    more than n_fft / 2 samples, a clamp whose square is a normal float32, a positive exponent."""
+    more than n_fft / 2 samples, a clamp whose square is a normal float32, a positive exponent.  ``loss``: every size is
+    built for both "l1" and "l2"."""
+    _dist_entry("", loss)
     return (stft_fused_supported(n_fft) and hop * 4 == n_fft and T > n_fft // 2 and T < 2 ** 30
             and (1 + T // hop) * (n_fft // 2 + 1) < 2 ** 31
             and float(clamp_eps) ** 2 >= float(torch.finfo(torch.float32).tiny) and power > 0)
 
 
 def stft_distance(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_fft: int, hop: int, clamp_eps: float,
-                  power: float, g_log: float, g_mag: float, want_grad: bool):
+                  power: float, g_log: float, g_mag: float, want_grad: bool, loss: str = "l1"):
     """One scale of the STFT-magnitude distance between ``x`` and ``y`` (B, C, T float32 HIP tensors) in one kernel.
 
     Returns ``(sums, G)``: ``sums`` = 2 float64 on the device, ``sum |p log10 max(|X|, eps) - p log10 max(|Y|, eps)|`` and
     ``sum | |X| - |Y| |`` over all B C N F elements; ``G`` = ``g_log`` d sums[0]/dX + ``g_mag`` d sums[1]/dX as a complex64
     tensor of logical shape (B, C, F, N) (the bin-contiguous memory ``stft_adjoint`` reads without a copy), or None
-    without ``want_grad``.  No spectrum is written, nothing is read back to the host."""
+    without ``want_grad``.  No spectrum is written, nothing is read back to the host.
+
+    ``loss="l2"``: the squared error (``nn.MSELoss``), ``sums`` = ``sum (p log10 max(|X|, eps) - p log10 max(|Y|, eps))^2``
+    and ``sum (|X| - |Y|)^2``, ``G`` their gradient with the same weights."""
+    entry = _dist_entry("at_stft_dist_f32", loss)
     _require_native_ok(x)
     _require_native_ok(y)
     if x.shape != y.shape or x.ndim != 3 or x.dtype != torch.float32 or y.dtype != torch.float32 or x.device != y.device:
@@ -641,30 +654,37 @@ def stft_distance(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_fft:
     G = None
     if want_grad:
         G = _alloc_retry(lambda: torch.empty((B, C, 1 + T // hop, n_fft // 2 + 1), dtype=torch.complex64, device=dev))
-    code = lib.at_stft_dist_f32(_native.ptr(x), _native.ptr(y), B * C, T, _native.ptr(window),
-                                _native.ptr(tables.stft_twiddles(n_fft, dev)), n_fft, hop, clamp_eps, power, g_log, g_mag,
-                                _native.ptr(G), _native.ptr(sums), _native.ptr(ws), ws.numel(), _native.current_stream(dev))
-    _native.check(code, "at_stft_dist_f32")
+    code = getattr(lib, entry)(_native.ptr(x), _native.ptr(y), B * C, T, _native.ptr(window),
+                               _native.ptr(tables.stft_twiddles(n_fft, dev)), n_fft, hop, clamp_eps, power, g_log, g_mag,
+                               _native.ptr(G), _native.ptr(sums), _native.ptr(ws), ws.numel(), _native.current_stream(dev))
+    _native.check(code, entry)
     return sums, (None if G is None else G.transpose(2, 3))
 
 
-def mel_distance_supported(n_fft: int, hop: int, T: int, n_mels: int, clamp_eps: float, power: float) -> bool:
+def mel_distance_supported(n_fft: int, hop: int, T: int, n_mels: int, clamp_eps: float, power: float,
+                           loss: str = "l1") -> bool:
     """The fused mel distance kernel (csrc/meldist.hip) takes this scale: the shapes of :func:`stft_distance_supported`,
-    1 <= n_mels <= n_fft / 4, a clamp (applied to mel, not to its square) that is a normal float32, a positive exponent."""
+    1 <= n_mels <= n_fft / 4, a clamp (applied to mel, not to its square) that is a normal float32, a positive exponent.
+    ``loss``: every size is built for both "l1" and "l2"."""
+    _dist_entry("", loss)
     return (stft_fused_supported(n_fft) and hop * 4 == n_fft and T > n_fft // 2 and T < 2 ** 30
             and (1 + T // hop) * (n_fft // 2 + 1) < 2 ** 31 and 1 <= n_mels <= n_fft // 4
             and float(clamp_eps) >= float(torch.finfo(torch.float32).tiny) and power > 0)
 
 
 def mel_distance(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_fft: int, hop: int, mel_tables, n_mels: int,
-                 clamp_eps: float, power: float, g_log: float, g_mag: float, want_grad: bool):
+                 clamp_eps: float, power: float, g_log: float, g_mag: float, want_grad: bool, loss: str = "l1"):
     """One scale of the mel-spectrogram distance between ``x`` and ``y`` (B, C, T float32 HIP tensors) in one kernel;
     ``mel_tables`` = ``tables.mel_dist_tables(...)``.
 
     Returns ``(sums, G)``: ``sums`` = 2 float64 on the device, ``sum |p log10 max(mel_x, eps) - p log10 max(mel_y, eps)|``
     and ``sum |mel_x - mel_y|`` over all B C N n_mels elements; ``G`` = ``g_log`` d sums[0]/dX + ``g_mag`` d sums[1]/dX as a
     complex64 tensor of logical shape (B, C, F, N) (the bin-contiguous memory ``stft_adjoint`` reads without a copy), or
-    None without ``want_grad``.  No spectrum and no mel tensor is written, nothing is read back to the host."""
+    None without ``want_grad``.  No spectrum and no mel tensor is written, nothing is read back to the host.
+
+    ``loss="l2"``: the squared error (``nn.MSELoss``), ``sums`` = ``sum (p log10 max(mel_x, eps) - p log10 max(mel_y, eps))^2``
+    and ``sum (mel_x - mel_y)^2``, ``G`` their gradient with the same weights."""
+    entry = _dist_entry("at_mel_dist_f32", loss)
     _require_native_ok(x)
     _require_native_ok(y)
     if x.shape != y.shape or x.ndim != 3 or x.dtype != torch.float32 or y.dtype != torch.float32 or x.device != y.device:
@@ -683,25 +703,26 @@ def mel_distance(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_fft: 
     G = None
     if want_grad:
         G = _alloc_retry(lambda: torch.empty((B, C, 1 + T // hop, n_fft // 2 + 1), dtype=torch.complex64, device=dev))
-    code = lib.at_mel_dist_f32(_native.ptr(x), _native.ptr(y), B * C, T, _native.ptr(window),
+    code = getattr(lib, entry)(_native.ptr(x), _native.ptr(y), B * C, T, _native.ptr(window),
                                _native.ptr(tables.stft_twiddles(n_fft, dev)), n_fft, hop, _native.ptr(bands), _native.ptr(w),
                                _native.ptr(spans), n_mels, clamp_eps, power, g_log, g_mag, _native.ptr(G), _native.ptr(sums),
                                _native.ptr(ws), ws.numel(), _native.current_stream(dev))
-    _native.check(code, "at_mel_dist_f32")
+    _native.check(code, entry)
     return sums, (None if G is None else G.transpose(2, 3))
 
 
-def stft_distance_dx_supported(n_fft: int, hop: int, T: int, clamp_eps: float, power: float) -> bool:
+def stft_distance_dx_supported(n_fft: int, hop: int, T: int, clamp_eps: float, power: float, loss: str = "l1") -> bool:
     """The waveform mode of the fused distance kernel takes every scale :func:`stft_distance_supported` takes."""
-    return stft_distance_supported(n_fft, hop, T, clamp_eps, power)
+    return stft_distance_supported(n_fft, hop, T, clamp_eps, power, loss)
 
 
 def stft_distance_dx(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_fft: int, hop: int, clamp_eps: float,
-                     power: float, g_log: float, g_mag: float):
+                     power: float, g_log: float, g_mag: float, loss: str = "l1"):
     """:func:`stft_distance` with the gradient taken all the way to the signal inside the kernel (csrc/dist_ola.h).
 
     Returns ``(sums, dx)``: ``sums`` as there, ``dx`` = ``g_log`` d sums[0]/dx + ``g_mag`` d sums[1]/dx, float32 (B, C, T).
-    No spectrum-shaped tensor exists at any time; ``dx`` is the only large allocation."""
+    No spectrum-shaped tensor exists at any time; ``dx`` is the only large allocation.  ``loss`` as there."""
+    entry = _dist_entry("at_stft_dist_dx_f32", loss)
     _require_native_ok(x)
     _require_native_ok(y)
     if x.shape != y.shape or x.ndim != 3 or x.dtype != torch.float32 or y.dtype != torch.float32 or x.device != y.device:
@@ -715,24 +736,27 @@ def stft_distance_dx(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_f
     ws = _workspace(nbytes, dev)
     sums = torch.empty(2, dtype=torch.float64, device=dev)
     dx = _alloc_retry(lambda: torch.empty((B, C, T), dtype=torch.float32, device=dev))
-    code = lib.at_stft_dist_dx_f32(_native.ptr(x), _native.ptr(y), B * C, T, _native.ptr(window),
-                                   _native.ptr(tables.stft_twiddles(n_fft, dev)), n_fft, hop, clamp_eps, power, g_log, g_mag,
-                                   _native.ptr(dx), _native.ptr(sums), _native.ptr(ws), ws.numel(), _native.current_stream(dev))
-    _native.check(code, "at_stft_dist_dx_f32")
+    code = getattr(lib, entry)(_native.ptr(x), _native.ptr(y), B * C, T, _native.ptr(window),
+                               _native.ptr(tables.stft_twiddles(n_fft, dev)), n_fft, hop, clamp_eps, power, g_log, g_mag,
+                               _native.ptr(dx), _native.ptr(sums), _native.ptr(ws), ws.numel(), _native.current_stream(dev))
+    _native.check(code, entry)
     return sums, dx
 
 
-def mel_distance_dx_supported(n_fft: int, hop: int, T: int, n_mels: int, clamp_eps: float, power: float) -> bool:
+def mel_distance_dx_supported(n_fft: int, hop: int, T: int, n_mels: int, clamp_eps: float, power: float,
+                              loss: str = "l1") -> bool:
     """The waveform mode of the fused mel distance kernel takes every scale :func:`mel_distance_supported` takes (all seven
-    sizes build without scratch; n_fft 2048 runs one workgroup per CU)."""
-    return mel_distance_supported(n_fft, hop, T, n_mels, clamp_eps, power)
+    sizes build without scratch for both losses; n_fft 2048 runs one workgroup per CU)."""
+    return mel_distance_supported(n_fft, hop, T, n_mels, clamp_eps, power, loss)
 
 
 def mel_distance_dx(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_fft: int, hop: int, mel_tables, n_mels: int,
-                    clamp_eps: float, power: float, g_log: float, g_mag: float):
+                    clamp_eps: float, power: float, g_log: float, g_mag: float, loss: str = "l1"):
     """:func:`mel_distance` with the gradient taken all the way to the signal inside the kernel (csrc/dist_ola.h).
 
-    Returns ``(sums, dx)``: ``sums`` as there, ``dx`` = ``g_log`` d sums[0]/dx + ``g_mag`` d sums[1]/dx, float32 (B, C, T)."""
+    Returns ``(sums, dx)``: ``sums`` as there, ``dx`` = ``g_log`` d sums[0]/dx + ``g_mag`` d sums[1]/dx, float32 (B, C, T).
+    ``loss`` as there."""
+    entry = _dist_entry("at_mel_dist_dx_f32", loss)
     _require_native_ok(x)
     _require_native_ok(y)
     if x.shape != y.shape or x.ndim != 3 or x.dtype != torch.float32 or y.dtype != torch.float32 or x.device != y.device:
@@ -749,11 +773,11 @@ def mel_distance_dx(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_ff
     ws = _workspace(nbytes, dev)
     sums = torch.empty(2, dtype=torch.float64, device=dev)
     dx = _alloc_retry(lambda: torch.empty((B, C, T), dtype=torch.float32, device=dev))
-    code = lib.at_mel_dist_dx_f32(_native.ptr(x), _native.ptr(y), B * C, T, _native.ptr(window),
-                                  _native.ptr(tables.stft_twiddles(n_fft, dev)), n_fft, hop, _native.ptr(bands), _native.ptr(w),
-                                  _native.ptr(spans), n_mels, clamp_eps, power, g_log, g_mag, _native.ptr(dx), _native.ptr(sums),
-                                  _native.ptr(ws), ws.numel(), _native.current_stream(dev))
-    _native.check(code, "at_mel_dist_dx_f32")
+    code = getattr(lib, entry)(_native.ptr(x), _native.ptr(y), B * C, T, _native.ptr(window),
+                               _native.ptr(tables.stft_twiddles(n_fft, dev)), n_fft, hop, _native.ptr(bands), _native.ptr(w),
+                               _native.ptr(spans), n_mels, clamp_eps, power, g_log, g_mag, _native.ptr(dx), _native.ptr(sums),
+                               _native.ptr(ws), ws.numel(), _native.current_stream(dev))
+    _native.check(code, entry)
     return sums, dx
 
 

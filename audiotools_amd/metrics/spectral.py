@@ -6,7 +6,8 @@ require gradients those run the fused forward kernels and their adjoints
 spectrum gradient in HBM.  ``MultiScaleSTFTLoss(fused=True)`` goes further: one kernel per scale takes both signals
 to the loss sums and dL/dX (``csrc/stftdist.hip``), no spectrum is written at all; ``MelSpectrogramLoss(fused=True)`` is
 the same for the mel distance (``csrc/meldist.hip``).  ``fused="waveform"`` also keeps dL/dX on chip: the kernel returns the
-loss sums and the gradient of the SIGNAL (``csrc/dist_ola.h``), backward is one multiplication."""
+loss sums and the gradient of the SIGNAL (``csrc/dist_ola.h``), backward is one multiplication.  The fused kernels exist for
+two norms: ``loss_fn=nn.L1Loss()`` and ``loss_fn=nn.MSELoss()``."""
 import typing
 
 import numpy as np
@@ -22,6 +23,10 @@ def _scales(window_lengths, match_stride, window_type):
             for w in window_lengths]
 
 
+# loss_fn types the fused distance kernels evaluate (exact types: a subclass may compute anything) -> their ``loss=`` keyword
+_FUSED_NORMS = {nn.L1Loss: "l1", nn.MSELoss: "l2"}
+
+
 def _log_and_linear(loss_fn, a, b, clamp_eps, power, log_weight, mag_weight):
     """log_weight * d(log10 clamp(a)^p, log10 clamp(b)^p) + mag_weight * d(a, b)
     (spectral.py:88-93, 188-193)."""
@@ -31,16 +36,16 @@ def _log_and_linear(loss_fn, a, b, clamp_eps, power, log_weight, mag_weight):
 
 
 class _StftDistance(torch.autograd.Function):
-    """One scale of the L1 STFT-magnitude distance as ONE kernel (``kernels.stft_distance``): the value from the two
+    """One scale of the L1 or L2 (``norm``) STFT-magnitude distance as ONE kernel (``kernels.stft_distance``): the value from the two
     signals, and -- only when the estimate needs a gradient -- dL/dX, which backward hands to the native STFT adjoint.
     Neither spectrum nor any intermediate of the loss exists in memory."""
 
     @staticmethod
-    def forward(ctx, est, ref, window, n_fft, hop, clamp_eps, power, log_weight, mag_weight):
+    def forward(ctx, est, ref, window, n_fft, hop, clamp_eps, power, log_weight, mag_weight, norm):
         B, C, T = est.shape
         count = B * C * (1 + T // hop) * (n_fft // 2 + 1)
         sums, G = kernels.stft_distance(est.detach(), ref.detach(), window, n_fft, hop, clamp_eps, power,
-                                        log_weight / count, mag_weight / count, ctx.needs_input_grad[0])
+                                        log_weight / count, mag_weight / count, ctx.needs_input_grad[0], loss=norm)
         ctx.save_for_backward(G, window)
         ctx.cfg = (n_fft, hop, T)
         return (sums[0] * (log_weight / count) + sums[1] * (mag_weight / count)).to(est.dtype)
@@ -49,7 +54,7 @@ class _StftDistance(torch.autograd.Function):
     def backward(ctx, grad_out):
         G, window = ctx.saved_tensors
         n_fft, hop, T = ctx.cfg
-        return (kernels.stft_adjoint(G, window, n_fft, hop, T) * grad_out,) + (None,) * 8
+        return (kernels.stft_adjoint(G, window, n_fft, hop, T) * grad_out,) + (None,) * 9
 
 
 class _StftDistanceWave(torch.autograd.Function):
@@ -57,20 +62,20 @@ class _StftDistanceWave(torch.autograd.Function):
     no dL/dX in memory, no adjoint launch, no clone and no fold in backward."""
 
     @staticmethod
-    def forward(ctx, est, ref, window, n_fft, hop, clamp_eps, power, log_weight, mag_weight):
+    def forward(ctx, est, ref, window, n_fft, hop, clamp_eps, power, log_weight, mag_weight, norm):
         B, C, T = est.shape
         count = B * C * (1 + T // hop) * (n_fft // 2 + 1)
         args = (est.detach(), ref.detach(), window, n_fft, hop, clamp_eps, power, log_weight / count, mag_weight / count)
         if ctx.needs_input_grad[0]:
-            sums, dx = kernels.stft_distance_dx(*args)
+            sums, dx = kernels.stft_distance_dx(*args, loss=norm)
             ctx.save_for_backward(dx)
         else:
-            sums, _ = kernels.stft_distance(*args, False)
+            sums, _ = kernels.stft_distance(*args, False, loss=norm)
         return (sums[0] * (log_weight / count) + sums[1] * (mag_weight / count)).to(est.dtype)
 
     @staticmethod
     def backward(ctx, grad_out):
-        return (ctx.saved_tensors[0] * grad_out,) + (None,) * 8
+        return (ctx.saved_tensors[0] * grad_out,) + (None,) * 9
 
 
 class MultiScaleSTFTLoss(nn.Module):
@@ -79,7 +84,8 @@ class MultiScaleSTFTLoss(nn.Module):
     ``loss_fn``.  ``weight`` is carried for the trainer, not applied here.
 
     ``fused=True`` (not in the reference) evaluates every scale that qualifies with the fused distance kernel: both
-    signals float32 HIP tensors of one shape, ``loss_fn`` an ``nn.L1Loss`` with mean reduction, at most one signal requiring
+    signals float32 HIP tensors of one shape, ``loss_fn`` an ``nn.L1Loss`` or an ``nn.MSELoss`` with mean reduction (exactly
+    these types; anything else runs unfused), at most one signal requiring
     a gradient, a power-of-two window of 32 ... 2048.  Such a scale does NOT touch ``stft_data`` of either signal; every
     other scale runs the code of ``fused=False``.  ``fused="waveform"``: the same scales, with the gradient of the signal
     from the kernel itself (no spectrum gradient in memory, no adjoint launch)."""
@@ -96,7 +102,7 @@ class MultiScaleSTFTLoss(nn.Module):
     def _fused_scale(self, x, y, s):
         """The scale's loss from the fused kernel, or None when the scale does not qualify."""
         xa, ya = x.audio_data, y.audio_data
-        if not (self.fused and type(self.loss_fn) is nn.L1Loss and self.loss_fn.reduction == "mean"
+        if not (self.fused and type(self.loss_fn) in _FUSED_NORMS and self.loss_fn.reduction == "mean"
                 and xa.is_cuda and ya.is_cuda and xa.dtype == ya.dtype == torch.float32 and xa.ndim == 3
                 and xa.shape == ya.shape and xa.device == ya.device):
             return None
@@ -106,13 +112,14 @@ class MultiScaleSTFTLoss(nn.Module):
         if (gx and gy) or wtype != (s.window_type or y.stft_params.window_type):
             return None
         supported = kernels.stft_distance_dx_supported if self.fused == "waveform" else kernels.stft_distance_supported
-        if not supported(s.window_length, s.hop_length, xa.shape[-1], self.clamp_eps, self.pow):
+        norm = _FUSED_NORMS[type(self.loss_fn)]
+        if not supported(s.window_length, s.hop_length, xa.shape[-1], self.clamp_eps, self.pow, norm):
             return None
-        est, ref = (ya, xa) if gy else (xa, ya)          # L1 is symmetric: the signal that needs a gradient is the estimate
+        est, ref = (ya, xa) if gy else (xa, ya)          # both norms are symmetric: the signal that needs a gradient is the estimate
         window = x.get_window(wtype, s.window_length, str(xa.device))
         fn = _StftDistanceWave if self.fused == "waveform" else _StftDistance
         return fn.apply(est, ref, window, s.window_length, s.hop_length, float(self.clamp_eps), float(self.pow),
-                        float(self.log_weight), float(self.mag_weight))
+                        float(self.log_weight), float(self.mag_weight), norm)
 
     def forward(self, x, y):
         total = 0.0
@@ -130,16 +137,16 @@ class MultiScaleSTFTLoss(nn.Module):
 
 
 class _MelDistance(torch.autograd.Function):
-    """One scale of the L1 mel-spectrogram distance as ONE kernel (``kernels.mel_distance``): the value from the two
+    """One scale of the L1 or L2 (``norm``) mel-spectrogram distance as ONE kernel (``kernels.mel_distance``): the value from the two
     signals, and -- only when the estimate needs a gradient -- dL/dX, which backward hands to the native STFT adjoint.
     Neither spectrum, neither mel tensor nor any intermediate of the loss exists in memory."""
 
     @staticmethod
-    def forward(ctx, est, ref, window, n_fft, hop, mel_tables, n_mels, clamp_eps, power, log_weight, mag_weight):
+    def forward(ctx, est, ref, window, n_fft, hop, mel_tables, n_mels, clamp_eps, power, log_weight, mag_weight, norm):
         B, C, T = est.shape
         count = B * C * (1 + T // hop) * n_mels
         sums, G = kernels.mel_distance(est.detach(), ref.detach(), window, n_fft, hop, mel_tables, n_mels, clamp_eps, power,
-                                       log_weight / count, mag_weight / count, ctx.needs_input_grad[0])
+                                       log_weight / count, mag_weight / count, ctx.needs_input_grad[0], loss=norm)
         ctx.save_for_backward(G, window)
         ctx.cfg = (n_fft, hop, T)
         return (sums[0] * (log_weight / count) + sums[1] * (mag_weight / count)).to(est.dtype)
@@ -148,28 +155,28 @@ class _MelDistance(torch.autograd.Function):
     def backward(ctx, grad_out):
         G, window = ctx.saved_tensors
         n_fft, hop, T = ctx.cfg
-        return (kernels.stft_adjoint(G, window, n_fft, hop, T) * grad_out,) + (None,) * 10
+        return (kernels.stft_adjoint(G, window, n_fft, hop, T) * grad_out,) + (None,) * 11
 
 
 class _MelDistanceWave(torch.autograd.Function):
     """:class:`_MelDistance` with the gradient of the signal formed inside the kernel (``kernels.mel_distance_dx``)."""
 
     @staticmethod
-    def forward(ctx, est, ref, window, n_fft, hop, mel_tables, n_mels, clamp_eps, power, log_weight, mag_weight):
+    def forward(ctx, est, ref, window, n_fft, hop, mel_tables, n_mels, clamp_eps, power, log_weight, mag_weight, norm):
         B, C, T = est.shape
         count = B * C * (1 + T // hop) * n_mels
         args = (est.detach(), ref.detach(), window, n_fft, hop, mel_tables, n_mels, clamp_eps, power, log_weight / count,
                 mag_weight / count)
         if ctx.needs_input_grad[0]:
-            sums, dx = kernels.mel_distance_dx(*args)
+            sums, dx = kernels.mel_distance_dx(*args, loss=norm)
             ctx.save_for_backward(dx)
         else:
-            sums, _ = kernels.mel_distance(*args, False)
+            sums, _ = kernels.mel_distance(*args, False, loss=norm)
         return (sums[0] * (log_weight / count) + sums[1] * (mag_weight / count)).to(est.dtype)
 
     @staticmethod
     def backward(ctx, grad_out):
-        return (ctx.saved_tensors[0] * grad_out,) + (None,) * 10
+        return (ctx.saved_tensors[0] * grad_out,) + (None,) * 11
 
 
 class MelSpectrogramLoss(nn.Module):
@@ -178,8 +185,8 @@ class MelSpectrogramLoss(nn.Module):
     ``window_lengths[i]`` (hop = window / 4).
 
     ``fused=True`` (not in the reference) evaluates every scale that qualifies with the fused mel distance kernel: both
-    signals float32 HIP tensors of one shape and sample rate, ``loss_fn`` an ``nn.L1Loss`` with mean reduction, at most one
-    signal requiring a gradient, a power-of-two window of 32 ... 2048 and at most window / 4 bands.  Such a scale does NOT
+    signals float32 HIP tensors of one shape and sample rate, ``loss_fn`` an ``nn.L1Loss`` or an ``nn.MSELoss`` with mean
+    reduction (exactly these types; anything else runs unfused), at most one signal requiring a gradient, a power-of-two window of 32 ... 2048 and at most window / 4 bands.  Such a scale does NOT
     touch ``stft_data`` of either signal; every other scale runs the code of ``fused=False``.  ``fused="waveform"``: the same
     scales, with the gradient of the signal from the kernel itself."""
 
@@ -198,7 +205,7 @@ class MelSpectrogramLoss(nn.Module):
     def _fused_scale(self, x, y, s, n_mels, fmin, fmax):
         """The scale's loss from the fused kernel, or None when the scale does not qualify."""
         xa, ya = x.audio_data, y.audio_data
-        if not (self.fused and type(self.loss_fn) is nn.L1Loss and self.loss_fn.reduction == "mean"
+        if not (self.fused and type(self.loss_fn) in _FUSED_NORMS and self.loss_fn.reduction == "mean"
                 and xa.is_cuda and ya.is_cuda and xa.dtype == ya.dtype == torch.float32 and xa.ndim == 3
                 and xa.shape == ya.shape and xa.device == ya.device and x.sample_rate == y.sample_rate):
             return None
@@ -208,16 +215,17 @@ class MelSpectrogramLoss(nn.Module):
         if (gx and gy) or wtype != (s.window_type or y.stft_params.window_type):
             return None
         supported = kernels.mel_distance_dx_supported if self.fused == "waveform" else kernels.mel_distance_supported
-        if not supported(s.window_length, s.hop_length, xa.shape[-1], n_mels, self.clamp_eps, self.pow):
+        norm = _FUSED_NORMS[type(self.loss_fn)]
+        if not supported(s.window_length, s.hop_length, xa.shape[-1], n_mels, self.clamp_eps, self.pow, norm):
             return None
         mel_tables = tables.mel_dist_tables(x.sample_rate, s.window_length, n_mels, fmin, fmax, xa.device)
         if mel_tables is None:
             return None
-        est, ref = (ya, xa) if gy else (xa, ya)          # L1 is symmetric: the signal that needs a gradient is the estimate
+        est, ref = (ya, xa) if gy else (xa, ya)          # both norms are symmetric: the signal that needs a gradient is the estimate
         window = x.get_window(wtype, s.window_length, str(xa.device))
         fn = _MelDistanceWave if self.fused == "waveform" else _MelDistance
         return fn.apply(est, ref, window, s.window_length, s.hop_length, mel_tables, n_mels, float(self.clamp_eps),
-                        float(self.pow), float(self.log_weight), float(self.mag_weight))
+                        float(self.pow), float(self.log_weight), float(self.mag_weight), norm)
 
     def forward(self, x, y):
         total = 0.0

@@ -336,7 +336,9 @@ def mel_dist_tables(sr, n_fft, n_mels, fmin, fmax, device):
     if key in _mel_units_unsupported:
         return None
     bins = mel_bin_table(sr, n_fft, n_mels, fmin, fmax, device)
-    spans = None if bins is None else mel_band_spans_np(mel_filters_np(sr, n_fft, n_mels, fmin, fmax))
+    if key not in _mel_spans:         # once per filterbank: the span form is a python loop over the bands (ms at 320 bands)
+        _mel_spans[key] = None if bins is None else mel_band_spans_np(mel_filters_np(sr, n_fft, n_mels, fmin, fmax))
+    spans = _mel_spans[key]
     if spans is None:
         _mel_units_unsupported.add(key)
         return None
@@ -344,6 +346,7 @@ def mel_dist_tables(sr, n_fft, n_mels, fmin, fmax, device):
 
 
 _mel_units_unsupported = set()
+_mel_spans = {}
 
 
 def mel_units_or_none(sr, n_fft, n_mels, fmin, fmax, device):

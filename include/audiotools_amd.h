@@ -214,6 +214,33 @@ int at_mel_dist_dx_f32(const float* x, const float* y, int64_t rows, int64_t T, 
                        float clamp_eps, float power, float g_log, float g_mag, float* dx, double* sums,
                        void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- fused distances, squared error: the four launches above with an MSE loss_fn --------------------------
+ * Replace, per scale of  audiotools/metrics/spectral.py:11-94  (MultiScaleSTFTLoss) and  :97-194  (MelSpectrogramLoss) with
+ * loss_fn = nn.MSELoss(), what the L1 entry points replace with nn.L1Loss().  Arguments, argument checks, return codes and
+ * workspace (the four at_*_dist*_workspace_bytes functions above) are those of the entry point without "_l2".  With a, b
+ * = |X|, |Y| (STFT) or mel_x, mel_y (mel), la = p log10 max(a, eps), lb likewise:
+ *   sums[0] = sum (la - lb)^2,   sums[1] = sum (a - b)^2      over the same elements as the L1 sums
+ *   coefficient per bin (STFT) or per band (mel: gmel[f,m]):
+ *     2 g_mag (a - b) + 2 g_log (la - lb) [a >= eps] p / (ln 10 a)
+ *   and from there as the L1 entry points: G = coef X / |X| (STFT), G[f,k] = (sum_m basis[m,k] gmel[f,m]) X[f,k] / |X[f,k]|
+ *   (mel), exactly 0 where |X|^2 < FLT_MIN, never NaN; dx from G as at_*_dist_dx_f32.  The caller passes g_log =
+ *   log_weight / count and g_mag = mag_weight / count (the 2 is applied inside).  No atomics: bit-equal for equal inputs.
+ */
+int at_stft_dist_l2_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                        int n_fft, int hop, float clamp_eps, float power, float g_log, float g_mag, float* G, double* sums,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+int at_mel_dist_l2_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                       int n_fft, int hop, const int* bin_bands, const float* bin_w, const int* band_span, int n_mels,
+                       float clamp_eps, float power, float g_log, float g_mag, float* G, double* sums,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+int at_stft_dist_dx_l2_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window,
+                           const float* twiddles, int n_fft, int hop, float clamp_eps, float power, float g_log, float g_mag,
+                           float* dx, double* sums, void* workspace, int64_t workspace_bytes, void* stream);
+int at_mel_dist_dx_l2_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                          int n_fft, int hop, const int* bin_bands, const float* bin_w, const int* band_span, int n_mels,
+                          float clamp_eps, float power, float g_log, float g_mag, float* dx, double* sums,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- fused SI-SDR loss: per-item loss and its gradient coefficients in one pass, gradient in one more ------
  * Replaces  audiotools/metrics/distance.py:43-131  (SISDRLoss.forward: the centring, alpha, target, residual, the two
  * energies, log10 and clamp -- a dozen passes over two (B, C*T) signals -- and their autograd replay).  ref is the FIRST

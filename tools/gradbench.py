@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Forward + backward of a magnitude loss through stft(): native kernels vs torch.stft autograd on the GPU.
 
-usage: gradbench.py [B [case]]    case: all (default) | stft | mel | dacmel | msstft | sisdr (its own shapes, whatever B)"""
+usage: gradbench.py [B [case]]    case: all (default) | stft | mel | dacmel | msstft | sisdr (its own shapes, whatever B) | mse"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -259,3 +259,50 @@ def run_sisdr(shape, rounds=7, reps=20):
 if CASE in ("all", "sisdr"):
     for shape in ((64, 1, 441000), (8, 1, 16000)):
         run_sisdr(shape)
+
+
+def run_mse(rounds=5):
+    """The squared-error recipes, forward + backward w.r.t. the estimate: MultiScaleSTFTLoss(loss_fn=nn.MSELoss()) at the default
+    scales and the 7-scale DAC mel recipe with nn.MSELoss(), fused=False / True / "waveform" alternating in one process, every window
+    between two HIP events; first the whole step, then every scale alone (a one-scale loss: what _fused_scale decides per scale)."""
+    from torch import nn
+    from audiotools_amd import metrics
+    mels, wins = [5, 10, 20, 40, 80, 160, 320], [32, 64, 128, 256, 512, 1024, 2048]
+    xs, ys = x[:32], (x[32:64] if B >= 64 else x[:32].flip(0)).clone()
+
+    def stft_loss(f, w=(2048, 512)):
+        return metrics.spectral.MultiScaleSTFTLoss(window_lengths=list(w), loss_fn=nn.MSELoss(), fused=f)
+
+    def mel_loss(f, m=mels, w=wins):
+        return metrics.spectral.MelSpectrogramLoss(n_mels=list(m), window_lengths=list(w), mel_fmin=[0] * len(w), mel_fmax=[None] * len(w),
+                                                   pow=1.0, mag_weight=0.0, loss_fn=nn.MSELoss(), fused=f)
+
+    cases = [("MSE MultiScaleSTFTLoss [2048, 512]", stft_loss, 20), ("MSE 7-scale MelSpectrogramLoss", mel_loss, 10)]
+    cases += [(f"MSE stft scale {w}", lambda f, w=w: stft_loss(f, (w,)), 20) for w in (2048, 512)]
+    cases += [(f"MSE mel scale {w} ({m} bands)", lambda f, m=m, w=w: mel_loss(f, (m,), (w,)), 20) for m, w in zip(mels, wins)]
+    for name, make, reps in cases:
+        losses = {f: make(f) for f in MODES}
+
+        def fn(f):
+            xa = xs.clone().requires_grad_(True)
+            val = losses[f](A.AudioSignal(xa, 44100), A.AudioSignal(ys, 44100))
+            val.backward()
+            node = val.grad_fn                     # the first scale's node: the fused Function or torch's own
+            while node.name() == "AddBackward0":
+                node = next(n for n, _ in node.next_functions if n is not None)
+            return xa.grad, node.name()
+
+        outs = {f: fn(f) for f in MODES}           # warm-up of all three paths
+        times = {f: [] for f in MODES}
+        for _ in range(rounds):
+            for f in MODES:
+                times[f].append(_timed(lambda: fn(f), reps))
+        for f in MODES:
+            ts = sorted(times[f])
+            diff = float((outs[f][0] - outs[False][0]).abs().max() / outs[False][0].abs().max())
+            print(f"{name} fwd + bwd, 32x2chx10s, fused={f}: median {ts[len(ts) // 2]:8.3f} ms  (min {ts[0]:.3f}, max {ts[-1]:.3f}; "
+                  f"{rounds} windows of {reps}); {outs[f][1]}; grad rel diff to unfused {diff:.2e}", flush=True)
+
+
+if CASE in ("all", "mse"):
+    run_mse()
