@@ -21,7 +21,7 @@ SHIP_LIB_PATH = os.path.join(LIB_DIR, "libaudiotools_amd.so")
 DEV_LIB_PATH = os.path.join(LIB_DIR, "libaudiotools_amd_dev.so")
 LIB_PATH = os.environ.get("AT_LIB_PATH") or (DEV_LIB_PATH if DEV_KNOBS else SHIP_LIB_PATH)
 CSRC_DIR = os.path.join(_HERE, "csrc")
-SOURCES = ["stft.hip", "istft.hip", "loudness.hip", "fir.hip", "firfft.hip", "irtools.hip", "specedit.hip", "fftconv.hip", "vocoder.hip", "stft_generic.hip", "longconv.hip", "resample_f16.hip", "stftdist.hip", "meldist.hip", "wavedist.hip"]
+SOURCES = ["stft.hip", "istft.hip", "loudness.hip", "fir.hip", "firfft.hip", "irtools.hip", "specedit.hip", "fftconv.hip", "vocoder.hip", "stft_generic.hip", "longconv.hip", "resample_f16.hip", "stftdist.hip", "meldist.hip", "meldist_wide.hip", "wavedist.hip"]
 
 _lib = None
 _lock = threading.Lock()
@@ -43,10 +43,11 @@ _NO_SLP = ["-fno-slp-vectorize"]
 # orders it for latency instead of register pressure (no spills, 237 -> 254 registers: the occupancy is the same) and
 # measures 2-3 % faster; every other source measured slower or equal with it (profiles/r03_notes.md, s81).
 _MAX_ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
-# stftdist.hip, meldist.hip, wavedist.hip: scalar FP32 throughout -- the packed-FP32 instructions are switched off for the whole source (nothing in it gains from them).
+# stftdist.hip, meldist.hip, meldist_wide.hip, wavedist.hip: scalar FP32 throughout -- the packed-FP32 instructions are switched off for the whole source (nothing in it gains from them).
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"stft.hip": _NO_SLP, "istft.hip": _NO_SLP + _MAX_ILP, "firfft.hip": _NO_SLP, "longconv.hip": _NO_SLP, "loudness.hip": _NO_SLP,
               "stft_generic.hip": _NO_SLP, "stftdist.hip": _NO_SLP + _NO_PK_F32, "meldist.hip": _NO_SLP + _NO_PK_F32,
+              "meldist_wide.hip": _NO_SLP + _NO_PK_F32,
               "wavedist.hip": _NO_SLP + _NO_PK_F32}
 LINK_FLAGS = ["-L/opt/rocm/lib", "-lrocfft", "-Wl,-rpath,/opt/rocm/lib"]
 
@@ -160,6 +161,12 @@ SIGNATURES = {
     "at_stft_dist_dx_l2_f32": (_i32, [_p, _p, _i64, _i64, _p, _p, _i32, _i32, _f32, _f32, _f32, _f32, _p, _p, _p, _i64, _p]),
     "at_mel_dist_l2_f32": (_i32, [_p, _p, _i64, _i64, _p, _p, _i32, _i32, _p, _p, _p, _i32, _f32, _f32, _f32, _f32, _p, _p, _p, _i64, _p]),
     "at_mel_dist_dx_l2_f32": (_i32, [_p, _p, _i64, _i64, _p, _p, _i32, _i32, _p, _p, _p, _i32, _f32, _f32, _f32, _f32, _p, _p, _p, _i64, _p]),
+    "at_mel_dist_wide_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32]),
+    "at_mel_dist_wide_dx_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32]),
+    "at_mel_dist_wide_f32": (_i32, [_p, _p, _i64, _i64, _p, _p, _i32, _i32, _p, _p, _p, _i32, _f32, _f32, _f32, _f32, _p, _p, _p, _i64, _p]),
+    "at_mel_dist_wide_l2_f32": (_i32, [_p, _p, _i64, _i64, _p, _p, _i32, _i32, _p, _p, _p, _i32, _f32, _f32, _f32, _f32, _p, _p, _p, _i64, _p]),
+    "at_mel_dist_wide_dx_f32": (_i32, [_p, _p, _i64, _i64, _p, _p, _i32, _i32, _p, _p, _p, _i32, _f32, _f32, _f32, _f32, _p, _p, _p, _i64, _p]),
+    "at_mel_dist_wide_dx_l2_f32": (_i32, [_p, _p, _i64, _i64, _p, _p, _i32, _i32, _p, _p, _p, _i32, _f32, _f32, _f32, _f32, _p, _p, _p, _i64, _p]),
     "at_sisdr_workspace_bytes": (_i64, [_i64, _i64]),
     "at_sisdr_f32": (_i32, [_p, _p, _i64, _i64, _i32, _i32, _i32, _f32, _p, _p, _p, _p, _i64, _p]),
     "at_sisdr_grad_f32": (_i32, [_p, _p, _i64, _i64, _p, _p, _p, _p, _p]),

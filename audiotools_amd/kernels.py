@@ -661,14 +661,23 @@ def stft_distance(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_fft:
     return sums, (None if G is None else G.transpose(2, 3))
 
 
+_MEL_WIDE_CAP = 512      # bands of the wide mel distance kernel (csrc/meldist_wide.hip: MAX_MELS)
+
+
+def _mel_entry(name: str, n_fft: int, n_mels: int) -> str:
+    """``at_mel_dist*`` for n_mels <= n_fft / 4, the ``at_mel_dist_wide*`` twin (same arguments) above that."""
+    return name if n_mels <= n_fft // 4 else name.replace("at_mel_dist_", "at_mel_dist_wide_")
+
+
 def mel_distance_supported(n_fft: int, hop: int, T: int, n_mels: int, clamp_eps: float, power: float,
                            loss: str = "l1") -> bool:
-    """The fused mel distance kernel (csrc/meldist.hip) takes this scale: the shapes of :func:`stft_distance_supported`,
-    1 <= n_mels <= n_fft / 4, a clamp (applied to mel, not to its square) that is a normal float32, a positive exponent.
-    ``loss``: every size is built for both "l1" and "l2"."""
+    """The fused mel distance kernels take this scale: the shapes of :func:`stft_distance_supported`, 1 <= n_mels <=
+    n_fft / 4 (csrc/meldist.hip: the target's bands in registers) or n_fft / 4 < n_mels <= min(2 n_fft, 512)
+    (csrc/meldist_wide.hip: the target's bands in LDS), a clamp (applied to mel, not to its square) that is a normal
+    float32, a positive exponent.  ``loss``: every size is built for both "l1" and "l2"."""
     _dist_entry("", loss)
     return (stft_fused_supported(n_fft) and hop * 4 == n_fft and T > n_fft // 2 and T < 2 ** 30
-            and (1 + T // hop) * (n_fft // 2 + 1) < 2 ** 31 and 1 <= n_mels <= n_fft // 4
+            and (1 + T // hop) * (n_fft // 2 + 1) < 2 ** 31 and 1 <= n_mels <= max(n_fft // 4, min(2 * n_fft, _MEL_WIDE_CAP))
             and float(clamp_eps) >= float(torch.finfo(torch.float32).tiny) and power > 0)
 
 
@@ -681,10 +690,12 @@ def mel_distance(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_fft: 
     and ``sum |mel_x - mel_y|`` over all B C N n_mels elements; ``G`` = ``g_log`` d sums[0]/dX + ``g_mag`` d sums[1]/dX as a
     complex64 tensor of logical shape (B, C, F, N) (the bin-contiguous memory ``stft_adjoint`` reads without a copy), or
     None without ``want_grad``.  No spectrum and no mel tensor is written, nothing is read back to the host.
+    ``n_mels > n_fft / 4`` runs the wide kernel (csrc/meldist_wide.hip), everything else the kernel of csrc/meldist.hip.
 
     ``loss="l2"``: the squared error (``nn.MSELoss``), ``sums`` = ``sum (p log10 max(mel_x, eps) - p log10 max(mel_y, eps))^2``
     and ``sum (mel_x - mel_y)^2``, ``G`` their gradient with the same weights."""
-    entry = _dist_entry("at_mel_dist_f32", loss)
+    entry = _mel_entry(_dist_entry("at_mel_dist_f32", loss), n_fft, n_mels)
+    ws_entry = _mel_entry("at_mel_dist_workspace_bytes", n_fft, n_mels)
     _require_native_ok(x)
     _require_native_ok(y)
     if x.shape != y.shape or x.ndim != 3 or x.dtype != torch.float32 or y.dtype != torch.float32 or x.device != y.device:
@@ -696,8 +707,8 @@ def mel_distance(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_fft: 
     if bands.numel() != n_fft // 2 + 1 or w.numel() != 2 * bands.numel() or spans.numel() != n_mels:
         raise ValueError("mel_distance: tables of another filterbank")
     lib = _native.lib()
-    nbytes = lib.at_mel_dist_workspace_bytes(B * C, T, n_fft, hop, n_mels)
-    _native.check(min(nbytes, 0), "at_mel_dist_workspace_bytes")
+    nbytes = getattr(lib, ws_entry)(B * C, T, n_fft, hop, n_mels)
+    _native.check(min(nbytes, 0), ws_entry)
     ws = _workspace(nbytes, dev)
     sums = torch.empty(2, dtype=torch.float64, device=dev)
     G = None
@@ -745,8 +756,8 @@ def stft_distance_dx(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_f
 
 def mel_distance_dx_supported(n_fft: int, hop: int, T: int, n_mels: int, clamp_eps: float, power: float,
                               loss: str = "l1") -> bool:
-    """The waveform mode of the fused mel distance kernel takes every scale :func:`mel_distance_supported` takes (all seven
-    sizes build without scratch for both losses; n_fft 2048 runs one workgroup per CU)."""
+    """The waveform mode of the fused mel distance kernels takes every scale :func:`mel_distance_supported` takes (all
+    sizes of both kernels build without scratch for both losses; n_fft 2048 runs one workgroup per CU)."""
     return mel_distance_supported(n_fft, hop, T, n_mels, clamp_eps, power, loss)
 
 
@@ -756,7 +767,8 @@ def mel_distance_dx(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_ff
 
     Returns ``(sums, dx)``: ``sums`` as there, ``dx`` = ``g_log`` d sums[0]/dx + ``g_mag`` d sums[1]/dx, float32 (B, C, T).
     ``loss`` as there."""
-    entry = _dist_entry("at_mel_dist_dx_f32", loss)
+    entry = _mel_entry(_dist_entry("at_mel_dist_dx_f32", loss), n_fft, n_mels)
+    ws_entry = _mel_entry("at_mel_dist_dx_workspace_bytes", n_fft, n_mels)
     _require_native_ok(x)
     _require_native_ok(y)
     if x.shape != y.shape or x.ndim != 3 or x.dtype != torch.float32 or y.dtype != torch.float32 or x.device != y.device:
@@ -768,8 +780,8 @@ def mel_distance_dx(x: torch.Tensor, y: torch.Tensor, window: torch.Tensor, n_ff
     if bands.numel() != n_fft // 2 + 1 or w.numel() != 2 * bands.numel() or spans.numel() != n_mels:
         raise ValueError("mel_distance_dx: tables of another filterbank")
     lib = _native.lib()
-    nbytes = lib.at_mel_dist_dx_workspace_bytes(B * C, T, n_fft, hop, n_mels)
-    _native.check(min(nbytes, 0), "at_mel_dist_dx_workspace_bytes")
+    nbytes = getattr(lib, ws_entry)(B * C, T, n_fft, hop, n_mels)
+    _native.check(min(nbytes, 0), ws_entry)
     ws = _workspace(nbytes, dev)
     sums = torch.empty(2, dtype=torch.float64, device=dev)
     dx = _alloc_retry(lambda: torch.empty((B, C, T), dtype=torch.float32, device=dev))

@@ -5,7 +5,8 @@ require gradients those run the fused forward kernels and their adjoints
 (``spectral._NativeStft`` / ``_NativeStftMel``), so a multi-scale mel loss never materialises a
 spectrum gradient in HBM.  ``MultiScaleSTFTLoss(fused=True)`` goes further: one kernel per scale takes both signals
 to the loss sums and dL/dX (``csrc/stftdist.hip``), no spectrum is written at all; ``MelSpectrogramLoss(fused=True)`` is
-the same for the mel distance (``csrc/meldist.hip``).  ``fused="waveform"`` also keeps dL/dX on chip: the kernel returns the
+the same for the mel distance (``csrc/meldist.hip``; filterbanks with more than window / 4 bands, such as 64 bands at every
+scale: ``csrc/meldist_wide.hip``).  ``fused="waveform"`` also keeps dL/dX on chip: the kernel returns the
 loss sums and the gradient of the SIGNAL (``csrc/dist_ola.h``), backward is one multiplication.  The fused kernels exist for
 two norms: ``loss_fn=nn.L1Loss()`` and ``loss_fn=nn.MSELoss()``."""
 import typing
@@ -186,7 +187,8 @@ class MelSpectrogramLoss(nn.Module):
 
     ``fused=True`` (not in the reference) evaluates every scale that qualifies with the fused mel distance kernel: both
     signals float32 HIP tensors of one shape and sample rate, ``loss_fn`` an ``nn.L1Loss`` or an ``nn.MSELoss`` with mean
-    reduction (exactly these types; anything else runs unfused), at most one signal requiring a gradient, a power-of-two window of 32 ... 2048 and at most window / 4 bands.  Such a scale does NOT
+    reduction (exactly these types; anything else runs unfused), at most one signal requiring a gradient, a power-of-two window of 32 ... 2048 and at most
+    max(window / 4, min(2 window, 512)) bands (above window / 4 the kernel that keeps the target's bands in LDS runs).  Such a scale does NOT
     touch ``stft_data`` of either signal; every other scale runs the code of ``fused=False``.  ``fused="waveform"``: the same
     scales, with the gradient of the signal from the kernel itself."""
 

@@ -241,6 +241,33 @@ int at_mel_dist_dx_l2_f32(const float* x, const float* y, int64_t rows, int64_t 
                           float clamp_eps, float power, float g_log, float g_mag, float* dx, double* sums,
                           void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- fused mel distance, wide filterbanks: the eight mel launches above for n_mels > n_fft/4 ----------------
+ * at_mel_dist_f32 and its variants keep the target's bands in registers and take n_mels <= n_fft/4.  These entry points
+ * park them in LDS (csrc/meldist_wide.hip) and take  1 <= n_mels <= min(2 n_fft, 512)  on power-of-two n_fft in 32 ... 1024
+ * (n_fft 2048 reaches 512 bands through at_mel_dist_f32).  Arguments, formulas, summation order of a band, argument checks,
+ * return codes and workspace layout are those of the entry point without "_wide"; an all-zero band (span count 0) has
+ * mel = 0 on both sides, adds 0 to both sums and has gradient 0 (and counts in rows N n_mels).  No atomics: bit-equal for
+ * equal inputs.  A workgroup asks for up to 108 KB of LDS (one per CU at the cap of n_mels, two at e.g. 80 bands on 256).
+ */
+int64_t at_mel_dist_wide_workspace_bytes(int64_t rows, int64_t T, int n_fft, int hop, int n_mels);
+int at_mel_dist_wide_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                         int n_fft, int hop, const int* bin_bands, const float* bin_w, const int* band_span, int n_mels,
+                         float clamp_eps, float power, float g_log, float g_mag, float* G, double* sums,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+int at_mel_dist_wide_l2_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                            int n_fft, int hop, const int* bin_bands, const float* bin_w, const int* band_span, int n_mels,
+                            float clamp_eps, float power, float g_log, float g_mag, float* G, double* sums,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+int64_t at_mel_dist_wide_dx_workspace_bytes(int64_t rows, int64_t T, int n_fft, int hop, int n_mels);
+int at_mel_dist_wide_dx_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window, const float* twiddles,
+                            int n_fft, int hop, const int* bin_bands, const float* bin_w, const int* band_span, int n_mels,
+                            float clamp_eps, float power, float g_log, float g_mag, float* dx, double* sums,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+int at_mel_dist_wide_dx_l2_f32(const float* x, const float* y, int64_t rows, int64_t T, const float* window,
+                               const float* twiddles, int n_fft, int hop, const int* bin_bands, const float* bin_w,
+                               const int* band_span, int n_mels, float clamp_eps, float power, float g_log, float g_mag,
+                               float* dx, double* sums, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- fused SI-SDR loss: per-item loss and its gradient coefficients in one pass, gradient in one more ------
  * Replaces  audiotools/metrics/distance.py:43-131  (SISDRLoss.forward: the centring, alpha, target, residual, the two
  * energies, log10 and clamp -- a dozen passes over two (B, C*T) signals -- and their autograd replay).  ref is the FIRST

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Forward + backward of a magnitude loss through stft(): native kernels vs torch.stft autograd on the GPU.
 
-usage: gradbench.py [B [case]]    case: all (default) | stft | mel | dacmel | msstft | sisdr (its own shapes, whatever B) | mse"""
+usage: gradbench.py [B [case]]    case: all (default) | stft | mel | dacmel | msstft | sisdr (its own shapes, whatever B) | mse | widemel"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -306,3 +306,50 @@ def run_mse(rounds=5):
 
 if CASE in ("all", "mse"):
     run_mse()
+
+
+def run_wide_mel(rounds=5):
+    """The 64-bands-at-every-scale mel recipe (windows 32 ... 2048), forward + backward w.r.t. the estimate: fused=False / True /
+    "waveform" alternating in one process, every window between two HIP events; the whole step, then every scale that needs the
+    wide kernel (csrc/meldist_wide.hip) alone.  "narrow routing": ``*_supported`` limited to n_mels <= n_fft / 4, i.e. the whole
+    step as it ran before the wide kernel existed (those scales unfused, the others fused)."""
+    from audiotools_amd import kernels, metrics
+    wins = [32, 64, 128, 256, 512, 1024, 2048]
+    xs, ys = x[:32], (x[32:64] if B >= 64 else x[:32].flip(0)).clone()
+    supported = kernels.mel_distance_supported
+
+    def mel_loss(f, w=wins):
+        return metrics.spectral.MelSpectrogramLoss(n_mels=[64] * len(w), window_lengths=list(w), mel_fmin=[0] * len(w),
+                                                   mel_fmax=[None] * len(w), pow=1.0, mag_weight=0.0, fused=f)
+
+    def narrow(n_fft, hop, T, n_mels, *rest):
+        return n_mels <= n_fft // 4 and supported(n_fft, hop, T, n_mels, *rest)
+
+    cases = [("64-band 7-scale MelSpectrogramLoss", mel_loss, 10, supported), ("the same, narrow routing", mel_loss, 10, narrow)]
+    cases += [(f"mel scale {w} (64 bands)", lambda f, w=w: mel_loss(f, (w,)), 20, supported) for w in wins if w < 256]
+    for name, make, reps, route in cases:
+        losses = {f: make(f) for f in MODES}
+
+        def fn(f):
+            xa = xs.clone().requires_grad_(True)
+            losses[f](A.AudioSignal(xa, 44100), A.AudioSignal(ys, 44100)).backward()
+            return xa.grad
+
+        kernels.mel_distance_supported = route
+        try:
+            outs = {f: fn(f) for f in MODES}           # warm-up of all three paths
+            times = {f: [] for f in MODES}
+            for _ in range(rounds):
+                for f in MODES:
+                    times[f].append(_timed(lambda: fn(f), reps))
+        finally:
+            kernels.mel_distance_supported = supported
+        for f in MODES:
+            ts = sorted(times[f])
+            diff = float((outs[f] - outs[False]).abs().max() / outs[False].abs().max())
+            print(f"{name} fwd + bwd, 32x2chx10s, fused={f}: median {ts[len(ts) // 2]:8.3f} ms  (min {ts[0]:.3f}, max {ts[-1]:.3f}; "
+                  f"{rounds} windows of {reps}); grad rel diff to unfused {diff:.2e}", flush=True)
+
+
+if CASE in ("all", "widemel"):
+    run_wide_mel()
